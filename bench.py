@@ -20,11 +20,16 @@ then one RCCL all-reduce of the partial chains inside the step; value = N*K*step
 
 --config c2 | c3 | c4 | c5 runs a BASELINE config as the headline line instead (c4 = 1000 x 25M FedYoGi,
 c5 = 10000 x 100M q-FedAvg streamed through a resident chunk of <= 1000 clients); at N>1 they are sharded
-the same way.  The default run also reports configs 4 and 5 sharded over the N ranks under
-``other_configs`` (so the driver's 4- and 8-GPU runs measure them at their BASELINE GPU counts), and at
-N=1 configs 1-3 plus each config's CPU leg.
+the same way.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times ``--steps`` rounds, writes the last round's outputs if ``--dump-outputs DIR``
+is given, and prints the line (``value``, ``ms_per_step`` and the roofline of those rounds' own kernel events).
+``--full`` adds every side measurement after the timed region (minutes): the card's telemetry, the sustained leg,
+configs 4 and 5 sharded over the N ranks under ``other_configs`` (so 4- and 8-GPU runs measure them at their
+BASELINE GPU counts), at N=1 configs 1-3 plus each config's CPU leg, and at N>1 the reassembly, the one-GPU
+reference, the multi-GPU check and the PCIe-inclusive round.
+
+Extra objects on the JSON line (``cpu_baseline`` and ``schema`` with --full):
   roofline     achieved algorithmic GB/s of the dominant kernel on one GPU (algorithmic bytes per launch,
                SURVEY §8d, over this rank's slice / mean launch time from HIP events on the launch stream)
                vs the 8 TB/s HBM3E peak; ``traffic`` = HBM bytes per launch from the rocprofv3 PMC summary
@@ -47,6 +52,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+DUMP_BYTES = 48 * 2**20  # --dump-outputs: all files together stay below this (larger outputs are sampled)
+DUMP_SEED = 20240607  # the sample's element indices: one fixed draw per (array length, sample size)
 
 # BASELINE.json configs as device workloads (config 1 is the host round, measured separately)
 CONFIGS = {
@@ -64,7 +71,18 @@ EXTRA_BYTES = {  # SURVEY §8d algorithmic bytes beyond the 4KP client read + 4P
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed rounds (ms_per_step = their wall time / steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed region also run every side measurement: the card's telemetry, the "
+                         "sustained leg, the drop-in figure, other_configs, the CPU legs, and at N > 1 the reassembly, "
+                         "RCCL probe, one-GPU reference, multi-GPU check and PCIe-inclusive round (minutes); without "
+                         "it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (the round's new model; FedYoGi also "
+                         "its m and v, q-FedAvg its delta, per-client norms and chain) as DIR/<name>.npy in float32 "
+                         "(float64 where the path computes in it); an output above its equal share of %d MiB is a fixed "
+                         "seeded sample of its elements.  Same arguments (an explicit --warmup included) = same inputs "
+                         "and step count, so two builds compare output for output" % (DUMP_BYTES // 2**20))
     ap.add_argument("--warmup", type=int, default=-1,
                     help="untimed warmup rounds; -1 (default): at least 3 and, at N = 1, at least 1 s of them, so the "
                          "timed region starts with the card's clocks settled (the line reports the count)")
@@ -531,12 +549,53 @@ class Workload:
                 kx.yogi_step(self.mean, y["last"], y["m"], y["v"], self.out, P, init=y["init"],
                              **{k: y[k] for k in ("eta", "tau", "beta", "omb", "omb2")})
 
+    def outputs(self) -> dict:
+        """What the last ``step`` left for its caller, by name (device tensors, this rank's slice): the round's new
+        model, and the state the policy carries into the next round."""
+        P = self.P
+        out = {"model": self.out[:P]}
+        if self.cmode and self.yogi is None and self.qf is None:
+            out["partial_sum"] = self.acc[:P]  # the all-reduced chain the model was finished from
+        if self.yogi is not None:
+            out.update(mean=self.mean[:P], yogi_m=self.yogi["m"][:P], yogi_v=self.yogi["v"][:P])
+        if self.qf is not None:
+            out.update(qfed_delta=self.qf["delta"][:P], qfed_sqnorm=self.qf["sq"], qfed_hs=self.qf["hs"])
+            if self.qf["chain"] is not None:
+                out["mean_chain"] = self.qf["chain"][:P]
+        return out
+
     def free(self):
         import torch
 
         self.xs = []
         self.acc = self.out = self.qf = self.yogi = self.mean = None
         torch.cuda.empty_cache()
+
+
+def dump_outputs(w: Workload, path: str, rank: int = 0, world: int = 1) -> dict:
+    """--dump-outputs: ``w.outputs()`` as ``path/<name>.npy`` (``<name>_rank<r>.npy`` at N > 1), float32 (float64 kept),
+    at most DUMP_BYTES in all.  Each array gets an equal share of that; one above its share is written as the sample
+    ``a[idx]``, ``idx`` = share / itemsize indices drawn once (with replacement, DUMP_SEED) from the array's length —
+    the same elements in every run of the same shape.  Returns {file: [elements written, elements of the output]}."""
+    import numpy as np
+    import torch
+
+    outs = w.outputs()
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (len(outs) * world) - 4096  # (every rank writes its slice; the .npy header)
+    written = {}
+    for name, t in outs.items():
+        t = t.detach().reshape(-1)
+        if t.dtype != torch.float64:
+            t = t.float()
+        n = max(1, share // t.element_size())
+        if t.numel() > n:
+            idx = np.random.default_rng([DUMP_SEED, t.numel(), n]).integers(0, t.numel(), size=n)
+            t = t[torch.from_numpy(idx).to(t.device)]
+        fn = name + (".npy" if world == 1 else "_rank%d.npy" % rank)
+        np.save(os.path.join(path, fn), t.cpu().numpy())
+        written[fn] = [int(t.numel()), int(outs[name].numel())]
+    return written
 
 
 def _sync_all(dev, world):
@@ -612,9 +671,10 @@ def _rest(w, steps, dev, rest_s=None):
     return 0.0
 
 
-def time_workload(w: Workload, steps: int, warmup: int, dev, world, backend, rest_s=None):
+def time_workload(w: Workload, steps: int, warmup: int, dev, world, backend, rest_s=None, card=True):
     """Warmup, then exactly ``steps`` rounds between barrier + synchronize; (wall s, mean dominant-kernel
-    ms), both max over ranks.  With ``--rest`` > 0 heavy regions start after that idle (every rank rests alike)."""
+    ms), both max over ranks.  With ``--rest`` > 0 heavy regions start after that idle (every rank rests alike).
+    ``card``: sample the card's telemetry over the region (a child process); False leaves ``w.card`` None."""
     import numpy as np
     import torch
 
@@ -635,18 +695,22 @@ def time_workload(w: Workload, steps: int, warmup: int, dev, world, backend, res
     w.warmup_rounds = warmup
     split = w.yogi is not None and not w.cmode  # FedYoGi: a third event between the mean and the YoGi step
     evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3 if split else 2)) for _ in range(steps)]
-    from fedscale_amd.cardstate import CardSampler
+    sampler = w.card_before = w.card = None
+    if card:
+        from fedscale_amd.cardstate import CardSampler
 
-    w.card_before = CardSampler(dev).read_once()
-    sampler = CardSampler(dev, period_s=0.02, process=True)  # a child process: no GIL contention with the launches
+        w.card_before = CardSampler(dev).read_once()
+        sampler = CardSampler(dev, period_s=0.02, process=True)  # a child process: no GIL contention with the launches
     _sync_all(dev, world)
-    sampler.start()
+    if sampler is not None:
+        sampler.start()
     t0 = time.perf_counter()
     for i in range(steps):
         w.step(evs[i])
     _sync_all(dev, world)
     wall = time.perf_counter() - t0
-    w.card = sampler.stop().summary()
+    if sampler is not None:
+        w.card = sampler.stop().summary()
     w.step_ms = [e[0].elapsed_time(e[1]) for e in evs]  # each timed round's dominant-kernel ms (this rank)
     kern_ms = float(np.mean(w.step_ms))
     w.split_ms = None
@@ -1059,6 +1123,7 @@ def sustained_leg(w: "Workload", dev, seconds: float, launches: int, est_ms: flo
 def main():
     global REST_S
     args = parse()
+    full = args.full  # every leg below the headline's timed region (and the card's telemetry over it) runs only then
     global HEADLINE_REST_S, CONFIG_SUSTAIN_S
     if args.config_sustain is not None:
         CONFIG_SUSTAIN_S = max(0.0, args.config_sustain)
@@ -1102,12 +1167,15 @@ def main():
     w = Workload(policy, K, P, rank, world, dev, args.seed, shards, weak=weak, budget_fraction=args.mem_fraction,
                  sets=sets, mean_chain={"auto": "auto", "on": True, "off": False}[args.mean_chain])
     (wall, kern_ms_max), kern_ms, kern_ms_ranks = time_workload(w, args.steps, args.warmup, dev, world,
-                                                                 args.dist_backend, rest_s=HEADLINE_REST_S)
+                                                                 args.dist_backend, rest_s=HEADLINE_REST_S, card=full)
+    dumped = None
+    if args.dump_outputs:  # the last timed step's outputs, before any later leg steps the workload again
+        dumped = dump_outputs(w, args.dump_outputs, rank, world)
     warmup_used = w.warmup_rounds  # --warmup -1: the count the auto warmup ran
     step_ms = list(w.step_ms)
     pg_world = dist.get_world_size() if world > 1 else 1
     strong = not weak and not w.cmode
-    card_state = {"before_timed_region": w.card_before, "timed_region": w.card, "rest_s": w.rest_s}
+    card_state = {"before_timed_region": w.card_before, "timed_region": w.card, "rest_s": w.rest_s} if full else None
     from fedscale_amd import kernels as kx
     if policy == "qfedavg":
         launches = len(w.passes) * kx.qfed_launches(w.ld, w.P, chain=bool(w.qf.get("chain") is not None))
@@ -1117,11 +1185,11 @@ def main():
         if policy == "fedyogi":
             launches += 1  # k_yogi_step after the mean
     sustained = None
-    if world == 1 and args.sustain > 0:
+    if full and world == 1 and args.sustain > 0:
         sustained = sustained_leg(w, dev, args.sustain, launches, wall * 1e3 / args.steps)
 
     reassembly_ms = None
-    if world > 1 and not args.no_reassemble and not w.cmode:  # egress: rebuild the global model (RCCL)
+    if full and world > 1 and not args.no_reassemble and not w.cmode:  # egress: rebuild the global model (RCCL)
         shards.collective_all_gather(w.out)  # warm the communicator
         _sync_all(dev, world)
         t0r = time.perf_counter()
@@ -1130,7 +1198,7 @@ def main():
         torch.cuda.synchronize(dev)
         reassembly_ms = _max_over_ranks([(time.perf_counter() - t0r) * 1e3 / 5], dev, world, args.dist_backend)[0]
     rccl_probe = None
-    if world > 1:  # what RCCL itself sees over the ranks (its own communicator; ranks sharing a GPU cannot open one)
+    if full and world > 1:  # what RCCL itself sees over the ranks (its own communicator: one rank per GPU)
         if args.dist_backend == "nccl":
             from fedscale_amd.state import spmd_rccl_probe
 
@@ -1158,13 +1226,14 @@ def main():
         _sync_all(dev, world)
         dist.barrier(group=cpu_group)
         if rank == 0:
-            one_gpu = one_gpu_reference(policy, K, P, dev, args.seed)
-            if policy == "fedavg":
+            if full:
+                one_gpu = one_gpu_reference(policy, K, P, dev, args.seed)
+            if policy == "fedavg":  # (the N > 1 line's `value` itself: also without --full)
                 inproc = run_inproc_bench(world, K, P, args.dist_backend, steps=args.steps, warmup=warmup_used)
         dist.barrier(group=cpu_group)
 
     drop_in = None
-    if world == 1 and policy == "fedavg" and not weak and not args.no_other_configs:
+    if full and world == 1 and policy == "fedavg" and not weak and not args.no_other_configs:
         # the same round through the drop-in (TorchModelAdapter begin_round / apply_round, every launch on the part's
         # stream) with the N > 1 line's in-process timing (fedscale_amd.inproc_bench): value(N) / value_drop_in(1)
         # then compares one methodology; outside the timed region, never `value`.  Run while the headline's
@@ -1183,7 +1252,7 @@ def main():
     del w
 
     other = None
-    if not args.no_other_configs and args.config == "headline":
+    if full and not args.no_other_configs and args.config == "headline":
         if world == 1:
             other = single_gpu_configs(dev, args.seed, shards, args.dist_backend, args.cpu_seconds)
         elif not shards.shards_clients:  # configs 4 and 5 at N GPUs (the driver's 4- and 8-GPU runs)
@@ -1194,7 +1263,7 @@ def main():
                     "c5", CONFIGS["c5"], dev, rank, world, shards, args.seed, args.dist_backend, steps=2, warmup=1)}
 
     selfcheck = None
-    if world > 1 and not args.no_selfcheck and args.dist_backend == "nccl":
+    if full and world > 1 and not args.no_selfcheck and args.dist_backend == "nccl":
         # the in-process drop-in (ShardedModelAdapter) over the node's N distinct GPUs, RCCL between them: what a
         # one-GPU box cannot run.  A child process with a deadline, after every rank has freed its workloads;
         # the other ranks wait at the barrier.  Outside the timed region; reported, never fatal.
@@ -1205,7 +1274,7 @@ def main():
         dist.barrier(group=cpu_group)
 
     pcie = cpu_base = None
-    if world > 1 and not args.no_pcie:
+    if full and world > 1 and not args.no_pcie:
         # the north star's two other figures beside the N-GPU one, outside the timed region, the other ranks waiting at
         # a host-side barrier: the rate including H2D and D2H copies over the N links (one aggregator process, pickled
         # payloads -> N GPUs -> get_weights), and the reference CPU aggregator (the oracle) on rank 0's host cores
@@ -1266,8 +1335,11 @@ def main():
                          "kernel_ms_per_launch_by_round": [round(x / launches, 4) for x in step_ms],
                          "traffic_key": "profiles/pmc_traffic.json entries[workload|C<resident_clients>|"
                                         "L<launches_per_step>|<build_id>] (null: no PMC pass of this shape and build)"},
-            "card_state": card_state,
         }
+        if card_state is not None:
+            res["card_state"] = card_state
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if sustained is not None:
             res["sustained"] = sustained
         if drop_in is not None:
@@ -1307,18 +1379,20 @@ def main():
             res["inproc_multi_gpu_check"] = selfcheck
         if other is not None:
             res["other_configs"] = other
-        if world == 1 and args.cpu_seconds > 0:
+        if full and world == 1 and args.cpu_seconds > 0:
             res["cpu_baseline"] = cpu_baseline(K, P, args.cpu_seconds, args.seed, policy)
         else:
             res["cpu_baseline"] = cpu_base
-            if world == 1 or args.cpu_seconds <= 0:
+            if not full or world == 1 or args.cpu_seconds <= 0:
                 res["cpu_legs_off"] = True
         if world == 1 and other is not None and "headline_model_pcie_inclusive" in other:
             res["pcie_inclusive"] = dict(other["headline_model_pcie_inclusive"], n_gpus=1)
         elif pcie is not None:
             res["pcie_inclusive"] = pcie
-        missing = check_line(res)
-        res["schema"] = {"complete": not missing, "missing": missing}
+        res["full"] = full
+        if full:  # (a line without --full carries the headline figure alone: the contract's fields, nothing to complete)
+            missing = check_line(res)
+            res["schema"] = {"complete": not missing, "missing": missing}
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier(group=cpu_group)

@@ -38,6 +38,54 @@ def test_default_arguments(monkeypatch):
     assert a.cfg["policy"] == "qfedavg" and a.cfg["params"] == 1000 and a.cfg["clients"] == 10_000
 
 
+def test_plain_run_is_the_headline_alone(monkeypatch):
+    """--full is off by default and --dump-outputs names a directory; --steps is the timed count as given."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+class _Outputs:
+    def __init__(self, **arrays):
+        self.arrays = arrays
+
+    def outputs(self):
+        return self.arrays
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """Small outputs are written whole; one above its share of DUMP_BYTES is the same seeded sample of its elements in
+    every run, its values taken from the array itself; everything is float32 except what the path holds in float64;
+    all files together stay within DUMP_BYTES."""
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * (4096 + 4000))  # a share of 1000 floats / 500 doubles each
+    g = torch.Generator().manual_seed(3)
+    big = torch.randn(5003, generator=g)
+    w = _Outputs(model=big, small=torch.arange(10, dtype=torch.float32), norms=torch.rand(501, generator=g).double())
+    wrote = bench.dump_outputs(w, str(tmp_path / "a"))
+    assert wrote == {"model.npy": [1000, 5003], "small.npy": [10, 10], "norms.npy": [500, 501]}
+    a = {n: np.load(tmp_path / "a" / n) for n in wrote}
+    assert a["model.npy"].dtype == np.float32 and a["norms.npy"].dtype == np.float64
+    np.testing.assert_array_equal(a["small.npy"], np.arange(10, dtype=np.float32))
+    assert set(a["model.npy"].tolist()) <= set(big.numpy().tolist()) and len(set(a["model.npy"].tolist())) > 800
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in wrote) <= bench.DUMP_BYTES
+    # the same elements again: a second dump of another array of that length picks the same indices
+    w2 = _Outputs(model=torch.arange(5003, dtype=torch.float32), small=w.arrays["small"], norms=w.arrays["norms"])
+    bench.dump_outputs(w2, str(tmp_path / "b"))
+    idx = np.load(tmp_path / "b" / "model.npy").astype(np.int64)
+    np.testing.assert_array_equal(a["model.npy"], big.numpy()[idx])
+    bench.dump_outputs(w, str(tmp_path / "c"))
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "model.npy"), a["model.npy"])
+    # N > 1: every rank writes its own files, and the shares shrink with the rank count
+    wrote = bench.dump_outputs(w, str(tmp_path / "d"), rank=1, world=2)
+    assert sorted(wrote) == ["model_rank1.npy", "norms_rank1.npy", "small_rank1.npy"] and wrote["model_rank1.npy"][0] < 500
+
+
 @pytest.mark.parametrize("policy", ["fedavg", "fedyogi", "qfedavg"])
 def test_cpu_leg_fields(policy):
     leg = bench.cpu_leg(policy, K=40, P=20_000, budget_s=0.2, seed=1, pool_n=4)
