@@ -315,6 +315,11 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
     TorchModelAdapter, so cohorts reduce concurrently and independently.  As in the reference,
     set_weights runs without client_training_results (:472)."""
 
+    #: opt-in: keep every upload's Auxo gradient signature (client_metadata.py:10-17) on the device and leave the
+    #: round's ``CohortSignatures`` in ``self.cohort_signatures[cohort_id]`` after the cohort's last result
+    #: (fedscale_amd/cohort_signature.py; INTEGRATION.md, "Auxo")
+    device_cohort_signatures = False
+
     def _is_first_result_in_round(self, cohort_id=0):
         return self.model_in_update[cohort_id] == 1
 
@@ -327,15 +332,29 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
             raise TypeError(f"model_wrapper[{cohort_id}] is {type(w).__name__}; the device path needs "
                             f"fedscale_amd's TorchModelAdapter")
         rounds = self.__dict__.setdefault("_device_rounds", {})
+        sigs = self.device_cohort_signatures
         if self._is_first_result_in_round(cohort_id) or cohort_id not in rounds:
-            rounds[cohort_id] = w.begin_round(self.tasks_round[cohort_id], "fedavg",
-                                              capacity=self.device_round_capacity)
-        rounds[cohort_id].add(results["update_weight"])
+            if sigs:
+                rounds[cohort_id] = w.begin_round(self.tasks_round[cohort_id], "fedavg",
+                                                  capacity=self.device_round_capacity, signatures=True)
+                self.__dict__.setdefault("_cohort_round_clients", {})[cohort_id] = []
+            else:
+                rounds[cohort_id] = w.begin_round(self.tasks_round[cohort_id], "fedavg",
+                                                  capacity=self.device_round_capacity)
+        rnd = rounds[cohort_id]
+        # decided per round, when it began (a ShardedRound, or a round begun with the switch off, keeps none)
+        keeps = getattr(rnd, "sig_plan", None) is not None
+        if keeps:
+            self._cohort_round_clients[cohort_id].append(results["client_id"])  # arrival order = signature rows
+        rnd.add(results["update_weight"])
         if self._is_last_result_in_round(cohort_id):
             K = self.tasks_round[cohort_id]
             w.apply_round(rounds.pop(cohort_id), float(np.float32(K)), float(K), client_training_results=None,
                           keep_mean=self.device_keep_mean)
             self.model_weights[cohort_id] = w.round_mean_weights()
+            if keeps:
+                self.__dict__.setdefault("cohort_signatures", {})[cohort_id] = rnd.cohort_signatures(
+                    self._cohort_round_clients.pop(cohort_id))
 
 
 class DeviceAggregator(DeviceAggregatorMixin):

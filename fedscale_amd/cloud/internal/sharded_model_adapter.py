@@ -229,7 +229,13 @@ class ShardedModelAdapter(TorchModelAdapter):
                 _native.call("fa_host_unregister", addr)
 
     # ---- rounds -----------------------------------------------------------------------------------
-    def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True) -> ShardedRound:
+    def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
+                    signatures: bool = False) -> ShardedRound:
+        if signatures:
+            raise NotImplementedError(
+                f"cohort signatures of a model sharded over {len(self.parts)} parts are not supported: the signature "
+                f"is the tail of the whole concatenated model (use a TorchModelAdapter on one GPU, or leave "
+                f"device_cohort_signatures off)")
         cap = capacity or self.staging_capacity
         if not cap and all(p.staging is not None and p.staging.capacity >= K for p in self.parts):
             cap = K  # the round fits the staging every part already holds (no free-memory query)

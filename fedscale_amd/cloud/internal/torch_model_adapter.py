@@ -450,10 +450,20 @@ class TorchModelAdapter(ModelAdapterBase):
         return (self.__class__, (self.get_model(), self.optimizer))
 
     # ---- device fast path -----------------------------------------------------------------------
-    def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True) -> DeviceRound:
+    def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
+                    signatures: bool = False) -> DeviceRound:
         """``keep_mean`` for q-FedAvg rounds: True fuses the FedAvg chain when the round spans several chunks
         (the staged updates are then gone by the end of the round), "always" in every round (the mean is then
-        independent of the staging's later reuse), False never (model_weights of such rounds raises)."""
+        independent of the staging's later reuse), False never (model_weights of such rounds raises).
+        ``signatures`` (FedAvg / FedBuff): the round also keeps every arrival's Auxo gradient signature against
+        the model it starts from (``DeviceRound.cohort_signatures``, fedscale_amd/cohort_signature.py)."""
+        plan = None
+        if signatures:
+            plan = self.__dict__.get("_signature_plan")
+            if plan is None:
+                from ...cohort_signature import signature_plan
+
+                plan = self._signature_plan = signature_plan(self.layout)
         cap = capacity or self.staging_capacity
         K_local = K
         if self.shards.shards_clients:  # this rank stages only its block of the arrivals
@@ -475,7 +485,7 @@ class TorchModelAdapter(ModelAdapterBase):
         return DeviceRound(self.layout, self.device, K, policy, capacity=want, staging=self.staging,
                            last_f32=snap.f32, last_i64=snap.side,
                            clients=self.shards if self.shards.shards_clients else None, mean_chain=chain,
-                           dstream=self.dstream)
+                           dstream=self.dstream, signature_plan=plan)
 
     def apply_round(self, rnd: DeviceRound, denom32: float, denom64: float, client_training_results=None,
                     keep_mean: bool = True):
@@ -587,6 +597,7 @@ class TorchModelAdapter(ModelAdapterBase):
         try:
             kx.call("fa_reduce_mirror", key[0] + h * x.shape[1] * 4, x.shape[1], n - h, L.P, None, key[5] or None,
                     key[3], key[4], denom32, flags, self.dstream.handle)
+            rnd._signatures_of(zc[0], zc[1], n)  # (a round begun with signatures) before the mirror is released
         finally:
             st.release_host_rows()  # the mirror's rows are rewritten only after the stream has passed the reads
         return True

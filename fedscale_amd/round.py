@@ -60,14 +60,25 @@ class DeviceRound:
     def __init__(self, layout: BucketLayout, device, K: int, policy: str, *, capacity: Optional[int] = None,
                  staging: Optional[ClientStaging] = None, last_f32: Optional[torch.Tensor] = None,
                  last_i64: Optional[torch.Tensor] = None, clients: Optional[ShardGroup] = None,
-                 mean_chain: bool = False, dstream: Optional[DeviceStream] = None):
+                 mean_chain: bool = False, dstream: Optional[DeviceStream] = None, signature_plan=None):
         """``mean_chain`` (q-FedAvg): fuse the plain FedAvg chain into the phase-1 kernel, so the round's
         mean (the reference's model_weights, aggregator.py:497-507) exists however many chunks the round
         spans (fa_qfed_accumulate's ``chain``: +1 add per element, measured 9 % on the kernel).
         ``dstream``: the DeviceStream of the owning adapter; every kernel and copy of the round is issued on
-        it (None: the caller's current stream)."""
+        it (None: the caller's current stream).
+        ``signature_plan`` (FedAvg / FedBuff; ``cohort_signature.signature_plan(layout)``): the round also keeps
+        every arrival's Auxo gradient signature (``sig``, [K, ldd] float16 in arrival order), computed from each
+        chunk's staged rows before the slots are reused (``cohort_signatures``)."""
         self.dstream = dstream
         self._init(layout, device, K, policy, capacity, staging, last_f32, last_i64, clients, mean_chain)
+        self.sig_plan, self.sig = signature_plan, None
+        if signature_plan is not None:
+            if policy == "qfedavg" or self.cg is not None:
+                raise NotImplementedError("cohort signatures: FedAvg / FedBuff rounds of one device only")
+            if last_f32 is None or last_i64 is None:
+                raise ValueError("cohort signatures need the round's starting model (last_f32 / last_i64)")
+            with self._on():
+                self.sig = torch.empty(self.K, signature_plan.ldd, dtype=torch.float16, device=self.device)
 
     def _on(self):
         """Context for GPU work of this round: its dstream unless already current (or none)."""
@@ -265,12 +276,31 @@ class DeviceRound:
         a64 = torch.from_numpy(self._w64[:n].copy()).to(self.device, non_blocking=True)
         return a32, a64
 
+    def _signatures_of(self, x, xi, n: int):
+        """The signatures of the chunk's n staged rows (x, xi: the device slots or the pinned mirror) into
+        ``sig[k0:k0 + n]``, k0 the arrival index of the chunk's first row — on the round's stream, before the
+        slots are rewritten."""
+        if self.sig_plan is not None and n > 0:
+            from . import cohort_signature as cs
+
+            cs.signature(x, xi, n, self.last_f32, self.last_i64, self.sig_plan, self.sig, row0=self.n_local - n)
+
+    def cohort_signatures(self, client_ids=()):
+        """The finished round's signatures (``CohortSignatures``; the round hands its ``sig`` buffer over)."""
+        from .cohort_signature import CohortSignatures
+
+        if self.sig_plan is None:
+            raise RuntimeError("the round was begun without signatures")
+        self._check_complete()
+        return CohortSignatures(self.sig, self.K, self.sig_plan.D, client_ids, self.dstream)
+
     @on_stream
     def _fold_chunk(self):
         """Fold the staged chunk into the running state (not the last chunk of the round)."""
         self.staging.drain()
         L, st, n = self.layout, self.staging, self.slot
         first = self.chunks_done == 0
+        self._signatures_of(st.x, st.xi, n)
         if self.policy in ("fedavg", "fedbuff"):
             if self.acc is None:
                 self.acc = torch.zeros(L.ld, dtype=torch.float32, device=self.device)
@@ -353,6 +383,7 @@ class DeviceRound:
             x, n, acc_in = x[self.head:], n - self.head, self.head_acc
         mode = 0 if self.policy == "fedavg" else 1
         try:
+            self._signatures_of(*(zc if zc is not None else (st.x, st.xi)), self.slot)
             if yogi is not None:
                 kx.reduce_yogi(x, n, L.P, a=a32, acc_in=acc_in, denom=denom32, out=out, **yogi)
             elif mirror is not None:
