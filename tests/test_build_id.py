@@ -76,3 +76,20 @@ def test_build_recompiles_a_library_without_the_trees_id(tmp_path, monkeypatch):
     assert buildinfo.build(str(lib)) is True
     assert len(ran) == 1 and buildinfo.embedded_id(str(lib)) == buildinfo.source_id()
     assert not [p for p in os.listdir(tmp_path) if ".tmp" in p]
+
+
+def test_build_leaves_one_hip_runtime_in_the_process():
+    """build() in a fresh interpreter: torch is imported before the library is loaded, so the library binds to the
+    HIP runtime torch brings along.  Loaded first, it pulls in the system's copy as a second runtime, and a smoke()
+    in the same process (``python __graft_entry__.py smoke``) then fails with "no current HIP device"."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import __graft_entry__ as e; e.build(); "
+            "print('HIPLIBS', sorted({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("HIPLIBS")][-1]
+    libs = eval(line.split(" ", 1)[1])
+    assert len(libs) == 1, f"build() left {len(libs)} HIP runtimes in the process: {libs}"
