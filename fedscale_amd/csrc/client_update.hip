@@ -675,7 +675,7 @@ extern "C" int fa_dp_noise_i64(const int64_t* const* x, double* const* out, cons
   return FA_OK;
 }
 
-// reference normal stream for host-side tests: z[i] for counter i (host twin in fedscale_amd/synth.py)
+// reference normal stream for host-side tests: z[i] for counter i (host twin: oracle.cpu_reference.dp_normals_ref)
 __global__ void k_dp_normals(float* out, int64_t n, uint64_t seed, int64_t off) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = noise_at(seed, (uint64_t)(off + i), 1.0f);

@@ -21,6 +21,8 @@ Reference anchors (paths relative to /root/reference):
 * FedProx client step ............... fedscale/cloud/execution/optimizers.py:6-10
 * local-DP clip + recover + noise ... examples/differential_privacy/customized_client.py:51-63,
                                       clip_norm.py:12-52 (pinned by tests/golden/gen_golden_client.py)
+* exact references for the client kernels (no reference code behind them: the kernels' own arithmetic restated):
+  dp_noise_hashes / dp_normals_ref, fma_f32 / sgd_prox_step_ref, dp_clip_exact (tests/test_client_oracle.py)
 
 Numerics notes (each reproduced deliberately):
 * accumulation is numpy, fp32, strictly in arrival order, allocating a new array each add;
@@ -344,3 +346,137 @@ def dp_privatize(state: "OrderedDict[str, np.ndarray]", is_param: Sequence[bool]
             raise ValueError("dp_privatize: sigma > 0 needs the noise draws")
         upload[n] = np.asarray(rec[n] + np.asarray(z, np.float32))
     return rec, upload, total
+
+
+# ------------------------------------------------------------------------------------------------
+# exact references for the client kernels (fedscale_amd/csrc/client_update.hip), numpy only
+# ------------------------------------------------------------------------------------------------
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _mix32(x: np.ndarray) -> np.ndarray:
+    """``mix32`` of client_update.hip on uint64 arrays that hold 32-bit values."""
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & _M32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & _M32
+    return x ^ (x >> np.uint64(16))
+
+
+def dp_noise_hashes(seed: int, e):
+    """The integer part of the counter-based N(0,1) generator (``normal_pair``): for every counter ``e`` (an
+    element of the noise stream) the two 32-bit hashes (h1, h2) of its pair ``j = e >> 1``, as uint32 arrays.
+    ``seed`` is taken modulo 2**64, as the ABI's uint64_t takes it."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    e = np.atleast_1d(np.asarray(e, dtype=np.uint64))
+    lo = np.array([seed & 0xFFFFFFFF], dtype=np.uint64)
+    hi = np.array([seed >> 32], dtype=np.uint64)
+    s = _mix32(lo ^ _mix32((hi + np.uint64(0x9E3779B9)) & _M32))
+    j = e >> np.uint64(1)
+    h1 = _mix32(s ^ _mix32((j & _M32) ^ _mix32(((j >> np.uint64(32)) + np.uint64(0x85EBCA6B)) & _M32)))
+    h2 = _mix32((h1 + np.uint64(0x27D4EB2F)) & _M32)
+    return h1.astype(np.uint32), h2.astype(np.uint32)
+
+
+def dp_normals_ref(seed: int, e) -> np.ndarray:
+    """Host twin of ``fa_dp_normals``: z[e] in float64.  The 24-bit uniforms and the angle are formed in fp32 as
+    the kernel forms them ((h1 >> 8) + 1 and h2 >> 8 are exact in fp32, and so are their products with 2**-24;
+    the angle is the fp32 product fp32(2 pi) * u2); logarithm, square root, sine and cosine are float64, so what
+    separates the device from this twin is the error of its logf, sqrtf and sincosf and one product rounding."""
+    e = np.atleast_1d(np.asarray(e, dtype=np.uint64))
+    h1, h2 = dp_noise_hashes(seed, e)
+    scale = np.float32(2.0 ** -24)
+    u1 = ((h1 >> np.uint32(8)).astype(np.float32) + np.float32(1.0)) * scale  # (0, 1]
+    u2 = (h2 >> np.uint32(8)).astype(np.float32) * scale                      # [0, 1)
+    angle = (np.float32(6.283185307179586) * u2).astype(np.float64)
+    r = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+    return np.where((e & np.uint64(1)).astype(bool), r * np.sin(angle), r * np.cos(angle))
+
+
+def fma_f32(a, x, y) -> np.ndarray:
+    """fp32 fused multiply-add ``fl32(y + a * x)`` with one rounding, without a hardware fma: the product of two
+    fp32 values is exact in float64, the float64 sum is rounded once, and rounding that to fp32 differs from the
+    fused result only where the float64 sum sits exactly on the midpoint of two neighbouring fp32 values while the
+    true sum does not; those elements are decided with exact rational arithmetic."""
+    from fractions import Fraction
+
+    a, x, y = np.broadcast_arrays(np.asarray(a, np.float32), np.asarray(x, np.float32), np.asarray(y, np.float32))
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = y.astype(np.float64) + a.astype(np.float64) * x.astype(np.float64)
+        r = s.astype(np.float32)
+        r64 = r.astype(np.float64)
+        other = np.nextafter(r, np.where(s > r64, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
+        tie = np.isfinite(s) & np.isfinite(r) & np.isfinite(other) & (s != r64) & \
+            ((r64 + other.astype(np.float64)) * 0.5 == s)
+    if tie.any():
+        r = r.copy()
+        for i in zip(*np.nonzero(tie)):
+            exact = Fraction(float(y[i])) + Fraction(float(a[i])) * Fraction(float(x[i]))
+            mid = Fraction(float(s[i]))
+            lo, hi = sorted((float(r[i]), float(other[i])))
+            if exact != mid:  # the float64 rounding made the tie: the true sum is on one side of it
+                r[i] = np.float32(hi if exact > mid else lo)
+    return r
+
+
+def sgd_prox_step_ref(params, grads, bufs, global_model, lr, momentum, dampening, weight_decay, flags, c,
+                      fma: bool):
+    """One fused step of ``k_sgd_prox`` (``sgd1`` op for op) on lists of fp32 arrays, with per-tensor scalars:
+    torch.optim.SGD (weight decay, momentum with dampening, nesterov; flags bit 0 nesterov, bit 1 first step,
+    where the buffer becomes the gradient and its old content is not read) and then the FedProx step
+    ``p + c * (p - w)`` in separately rounded ops.  ``fma``: every ``y + a * x`` of the SGD part is one fused
+    multiply-add (``fma_f32``); otherwise product and sum are rounded in turn.  ``bufs[i]`` may be None where
+    momentum[i] == 0, ``global_model`` None for no proximal step.  Returns (new params, new buffers)."""
+    f32 = np.float32
+
+    def axpy(a, x, y):
+        return fma_f32(a, x, y) if fma else y + f32(a) * x
+
+    out_p, out_m = [], []
+    for i, (p, g) in enumerate(zip(params, grads)):
+        p, g = np.asarray(p, f32), np.asarray(g, f32)
+        k_lr, k_mom, k_wd = f32(lr[i]), f32(momentum[i]), f32(weight_decay[i])
+        omd = f32(1.0 - float(dampening[i]))  # the double 1 - dampening, rounded to fp32 once
+        nesterov, first = bool(int(flags[i]) & 1), bool(int(flags[i]) & 2)
+        m = None if bufs is None or bufs[i] is None else np.asarray(bufs[i], f32)
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = g
+            if k_wd != 0:
+                d = axpy(k_wd, p, d)
+            if k_mom != 0:
+                m = d.copy() if first else axpy(omd, d, m * k_mom)
+                d = axpy(k_mom, m, d) if nesterov else m
+            p = axpy(-k_lr, d, p)
+            if global_model is not None:
+                p = p + f32(c) * (p - np.asarray(global_model[i], f32))
+        out_p.append(np.asarray(p, f32))
+        out_m.append(None if m is None else np.asarray(m, f32))
+    return out_p, out_m
+
+
+def dp_clip_exact(params, last, max_norm: float, norm_inf: bool = False) -> dict:
+    """clip_norm.py:32-52 with exactly rounded sums, the value ``fa_dp_clip_coef`` owes wherever its own fp64
+    summation error cannot move an fp32 rounding: d = fp32(p - last) (p where last[t] is None), S_t the exactly
+    rounded sum of the float64 squares (math.fsum), nt = fp32(sqrt(S_t)), total = fp32(sqrt(fsum(nt**2))),
+    coef = fp32(max_norm) / (total + fp32(1e-6)) in fp32, apply = coef < 1.  ``norm_inf``: the exact maximum of
+    |d|, NaN propagating; an empty tensor counts as 0.  Returns a dict with d, S, nt, S_total, total, coef, apply."""
+    import math
+
+    f32 = np.float32
+    T = len(params)
+    last = [None] * T if last is None else list(last)
+    d = [np.asarray(p, f32).reshape(-1) if l is None else
+         np.asarray(p, f32).reshape(-1) - np.asarray(l, f32).reshape(-1) for p, l in zip(params, last)]
+    if norm_inf:
+        S = [float("nan") if np.isnan(x).any() else float(np.abs(x).max(initial=0.0)) for x in d]
+        nt = [f32(s) for s in S]
+        S_total = float("nan") if any(math.isnan(s) for s in S) else max(S, default=0.0)
+        total = f32(S_total)
+    else:
+        S = [math.fsum((x.astype(np.float64) ** 2).tolist()) for x in d]
+        nt = [f32(math.sqrt(s)) for s in S]
+        S_total = math.fsum(float(v) ** 2 for v in nt)
+        total = f32(math.sqrt(S_total)) if T else f32(0.0)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        coef = f32(max_norm) / (total + f32(1e-6))
+    return dict(d=d, S=S, nt=nt, S_total=S_total, total=total, coef=coef, apply=bool(T > 0 and coef < 1))

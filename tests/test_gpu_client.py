@@ -276,12 +276,14 @@ def _sgd_model(seed, device):
 def test_fused_sgd_prox_step_matches_torch_sgd_then_fedprox(gpu_device, momentum, nesterov, wd, damp):
     """ClientOptimizer.step_and_update == torch.optim.SGD.step() + update_client_weight (torch_client.py:
     236-240, optimizers.py:6-10) over 4 local steps, one parameter without a gradient: parameters and
-    momentum buffers within the north-star fp32 tolerance (rtol 1e-5, atol 1e-6) for both variants, and
-    bit-exact to torch's foreach SGD on the GPU with fma (the default: torch's alpha-adds are contracted)."""
+    momentum buffers within the north-star fp32 tolerance (rtol 1e-5, atol 1e-6) for both variants,
+    bit-exact to torch's foreach SGD on the GPU with fma (the default: torch's alpha-adds are contracted), and
+    with fma=False bit-exact to the CPU oracle's separately rounded step (oracle.cpu_reference.sgd_prox_step_ref)."""
     import argparse
     import copy
 
     from fedscale_amd.cloud.execution.optimizers import ClientOptimizer
+    from oracle.cpu_reference import fedprox_update, sgd_prox_step_ref
 
     conf = argparse.Namespace(gradient_policy="fed-prox", learning_rate=0.05, proxy_mu=0.1)
     ref, g = _sgd_model(7, gpu_device)
@@ -293,12 +295,21 @@ def test_fused_sgd_prox_step_matches_torch_sgd_then_fedprox(gpu_device, momentum
         kw = dict(lr=conf.learning_rate, momentum=momentum, weight_decay=wd, nesterov=nesterov, dampening=damp)
         opt_r, opt_o = torch.optim.SGD(r.parameters(), **kw), torch.optim.SGD(ours.parameters(), **kw)
         gg = torch.Generator().manual_seed(11)
+        host_p = [p.detach().cpu().numpy().copy() for p in ref.parameters()]  # the CPU oracle's state
+        host_m = [None] * len(host_p)
         for step in range(4):
             for i, (pr, po) in enumerate(zip(r.parameters(), ours.parameters())):
                 if i == 3:  # no gradient: SGD skips it, FedProx still moves it
                     pr.grad = po.grad = None
+                    host_p[i] = fedprox_update([host_p[i]], [glob[i].cpu().numpy()], conf.learning_rate,
+                                               conf.proxy_mu)[0]
                     continue
-                gr = torch.randn(pr.shape, generator=gg).to(gpu_device)
+                gr = torch.randn(pr.shape, generator=gg)
+                flags = [(1 if nesterov else 0) | (2 if step == 0 else 0)]
+                (host_p[i],), (host_m[i],) = sgd_prox_step_ref(
+                    [host_p[i]], [gr.numpy()], [host_m[i]], [glob[i].cpu().numpy()], [conf.learning_rate],
+                    [momentum], [damp], [wd], flags, np.float32(conf.learning_rate * conf.proxy_mu), False)
+                gr = gr.to(gpu_device)
                 pr.grad, po.grad = gr.clone(), gr.clone()
             opt_r.step()
             for idx, param in enumerate(r.parameters()):  # optimizers.py:8-10, literally
@@ -314,6 +325,12 @@ def test_fused_sgd_prox_step_matches_torch_sgd_then_fedprox(gpu_device, momentum
                 torch.testing.assert_close(bo, br, rtol=1e-5, atol=1e-6)
                 ok &= torch.equal(bo, br)
         exact[fma] = ok
+        if not fma:
+            for i, po in enumerate(ours.parameters()):
+                assert np.array_equal(po.detach().cpu().numpy().view(np.uint32), host_p[i].view(np.uint32)), i
+                if host_m[i] is not None:
+                    bo = opt_o.state[po]["momentum_buffer"].cpu().numpy()
+                    assert np.array_equal(bo.view(np.uint32), host_m[i].view(np.uint32)), i
     assert exact[True], "fma variant: expected bit-exact to torch SGD + FedProx on the GPU"
     print(f"[sgd-prox] momentum={momentum} nesterov={nesterov} wd={wd} damp={damp}: bit-exact vs torch on GPU "
           f"fma={exact[True]} rounded={exact[False]}")
