@@ -81,6 +81,11 @@ class DeviceAggregatorMixin:
     #: torch's intra-op pool, gRPC work), for ~7 us on config 1's round (profiles/r03_numa_probe.log).  When on,
     #: torch's intra-op thread count is lowered to the node's CPUs and the binding is logged
     device_numa_bind = False
+    #: opt-in: "float16" / "bfloat16" — the executors upload their float32 entries in 16 bits
+    #: (fedscale_amd/cloud/execution/half_upload.py: lossy on the wire, exact from there on); staged in HBM as
+    #: 16-bit rows and reduced in fp32 (fedscale_amd/half_round.py).  FedAvg, FedBuff and fed-yogi; q-FedAvg,
+    #: device_shards and cohort signatures are refused with it
+    device_upload_dtype = None
 
     _device_round = None
 
@@ -124,11 +129,14 @@ class DeviceAggregatorMixin:
             from ..internal.sharded_model_adapter import ShardedModelAdapter
 
             opt = TorchServerOptimizer(self.args.gradient_policy, self.args, devs[0])
-            self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs)
+            # (16-bit uploads are refused by a sharded adapter; unset, the call is what it was)
+            kw = {} if self.device_upload_dtype is None else {"upload_dtype": self.device_upload_dtype}
+            self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
         else:
             dev = devs[0] if devs else self._aggregation_device()
             opt = TorchServerOptimizer(self.args.gradient_policy, self.args, dev)
-            self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev)
+            kw = {} if self.device_upload_dtype is None else {"upload_dtype": self.device_upload_dtype}
+            self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
             if self.device_numa_bind:
                 from ...hostnuma import bind_to_gpu
 

@@ -134,10 +134,27 @@ class TorchModelAdapter(ModelAdapterBase):
     ``apply_round`` of a round that exposes no device state (``_round_exposes_device_state``), whose results every
     public reader waits for by itself."""
 
+    #: "float16" / "bfloat16": the clients' float32 entries arrive in 16 bits (None: float32 uploads)
+    upload_dtype = None
+
     def __init__(self, model: torch.nn.Module, optimizer=None, device=None, shards: Optional[ShardGroup] = None,
-                 staging_capacity: Optional[int] = None, _load_from=None, dstream: Optional[DeviceStream] = None):
+                 staging_capacity: Optional[int] = None, _load_from=None, dstream: Optional[DeviceStream] = None,
+                 upload_dtype: Optional[str] = None):
+        """``upload_dtype`` ("float16" / "bfloat16"; None: float32 uploads, as the reference's): clients upload
+        their float32 entries in 16 bits (fedscale_amd/cloud/execution/half_upload.py); ``begin_round`` then
+        returns a ``HalfRound`` over a ``HalfStaging`` (fedscale_amd/half_round.py)."""
         self.model = model
         self.optimizer = optimizer
+        self.upload_dtype = None
+        if upload_dtype is not None:
+            from ...half_round import refuse
+            from ...kernels_half import row_dtype
+
+            self.upload_dtype = "float16" if row_dtype(upload_dtype)[0] == torch.float16 else "bfloat16"
+            if shards is not None and shards.world != 1:
+                raise refuse("a sharded model or client-sharded ranks (ShardGroup)", self.upload_dtype)
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse("the q-fedavg server optimizer", self.upload_dtype)
         self.device = _resolve_device(device)
         if dstream is not None and dstream.device != self.device:
             raise ValueError(f"dstream is on {dstream.device}, the adapter on {self.device}")
@@ -447,6 +464,8 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if self.upload_dtype is not None:
+            return (self.__class__, (self.get_model(), self.optimizer, None, None, None, None, None, self.upload_dtype))
         return (self.__class__, (self.get_model(), self.optimizer))
 
     # ---- device fast path -----------------------------------------------------------------------
@@ -457,6 +476,8 @@ class TorchModelAdapter(ModelAdapterBase):
         independent of the staging's later reuse), False never (model_weights of such rounds raises).
         ``signatures`` (FedAvg / FedBuff): the round also keeps every arrival's Auxo gradient signature against
         the model it starts from (``DeviceRound.cohort_signatures``, fedscale_amd/cohort_signature.py)."""
+        if self.upload_dtype is not None:
+            return self._begin_half_round(K, policy, capacity, signatures)
         plan = None
         if signatures:
             plan = self.__dict__.get("_signature_plan")
@@ -486,6 +507,28 @@ class TorchModelAdapter(ModelAdapterBase):
                            last_f32=snap.f32, last_i64=snap.side,
                            clients=self.shards if self.shards.shards_clients else None, mean_chain=chain,
                            dstream=self.dstream, signature_plan=plan)
+
+    def _begin_half_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool):
+        """``begin_round`` of an adapter with ``upload_dtype``: a ``HalfRound`` over a ``HalfStaging`` whose default
+        capacity is computed from 2-byte rows.  The combinations the 16-bit path does not take are refused here."""
+        from ...half_round import HalfRound, HalfStaging, default_capacity16, refuse
+
+        if signatures:
+            raise refuse("cohort signatures", self.upload_dtype)
+        if policy not in ("fedavg", "fedbuff"):
+            raise refuse(f"a {policy} round", self.upload_dtype)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            want = default_capacity16(self.layout, K, self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = HalfStaging(self.layout, self.device, want, self.upload_dtype, dstream=self.dstream)
+        return HalfRound(self.layout, self.device, K, policy, staging=self.staging, capacity=want,
+                         dstream=self.dstream)
 
     def apply_round(self, rnd: DeviceRound, denom32: float, denom64: float, client_training_results=None,
                     keep_mean: bool = True):
@@ -570,6 +613,8 @@ class TorchModelAdapter(ModelAdapterBase):
         every operand, fa_device.h) is paid once per (rows, model buffer, snapshot) triple and cached.  False:
         the round does not qualify (the caller takes finalize_mean)."""
         L = self.layout
+        if self.upload_dtype is not None:  # a HalfRound has no pinned mirror of its rows
+            return False
         if (not self.SMALL_ROUND_FINISH or host is None or L.Q or rnd.policy != "fedavg" or rnd.chunks_done
                 or rnd.cg is not None):
             return False
