@@ -86,8 +86,25 @@ class DeviceAggregatorMixin:
     #: 16-bit rows and reduced in fp32 (fedscale_amd/half_round.py).  FedAvg, FedBuff and fed-yogi; q-FedAvg,
     #: device_shards and cohort signatures are refused with it
     device_upload_dtype = None
+    #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
+    #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
+    #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
+    #: device_upload_dtype, the async and the cohort mixin are refused with it
+    device_clip_norm = None
+    #: with device_clip_norm: Gaussian noise of standard deviation multiplier * M / K on the clipped mean (0: none)
+    device_clip_noise_multiplier = 0.0
+    #: seed of that noise stream
+    device_clip_seed = 0
 
     _device_round = None
+
+    def _clip_spec(self):
+        """The ``ClipSpec`` of this aggregator's rounds (None: ``device_clip_norm`` is not set)."""
+        if self.device_clip_norm is None:
+            return None
+        from ...clip_round import ClipSpec
+
+        return ClipSpec(self.device_clip_norm, self.device_clip_noise_multiplier, self.device_clip_seed)
 
     # same predicates as aggregator.py:430-434 (defined here too so the mixin also works standalone)
     def _is_first_result_in_round(self):
@@ -273,9 +290,11 @@ class DeviceAggregatorMixin:
         rnd = self._device_round
         if rnd is None or self._is_first_result_in_round():
             w = self._wrapper()
+            clip = self._clip_spec()
+            kw = {} if clip is None else {"clip": clip}  # (unset, the call is what it was)
             rnd = self._device_round = w.begin_round(self.tasks_round, self._device_policy(),
                                                      capacity=self.device_round_capacity,
-                                                     keep_mean=self.device_keep_mean)
+                                                     keep_mean=self.device_keep_mean, **kw)
         if rnd.policy == "qfedavg":
             a = self._wrapper().optimizer.args  # optimizers.py:69 reads the live args at step time
             rnd.add(results["update_weight"], loss=results["moving_loss"], learning_rate=a.learning_rate,
@@ -298,6 +317,10 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
     """FedBuff (async_aggregator.py:115-137): staleness-weighted accumulate, divide by the weight sum."""
 
     def update_weight_aggregation(self, results):
+        if self.device_clip_norm is not None:
+            from ...clip_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         w = self._wrapper()
         # async_aggregator.py:125-126 — Python-float weight and denominator
         s = 1 / (1 + self.round - self.client_task_model_version[results["client_id"]]) ** 0.5
@@ -335,6 +358,10 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
         return self.model_in_update[cohort_id] == self.tasks_round[cohort_id]
 
     def update_weight_aggregation(self, results, cohort_id=0):
+        if self.device_clip_norm is not None:
+            from ...clip_round import refuse
+
+            raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         w = self.model_wrapper[cohort_id]
         if not isinstance(w, TorchModelAdapter):
             raise TypeError(f"model_wrapper[{cohort_id}] is {type(w).__name__}; the device path needs "

@@ -234,7 +234,11 @@ class ShardedModelAdapter(TorchModelAdapter):
 
     # ---- rounds -----------------------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
-                    signatures: bool = False) -> ShardedRound:
+                    signatures: bool = False, clip=None) -> ShardedRound:
+        if clip is not None:  # norm-clipped rounds (fedscale_amd/clip_round.py): one whole model on one device
+            from ...clip_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)")
         if signatures:
             raise NotImplementedError(
                 f"cohort signatures of a model sharded over {len(self.parts)} parts are not supported: the signature "

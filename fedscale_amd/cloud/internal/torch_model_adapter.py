@@ -136,6 +136,8 @@ class TorchModelAdapter(ModelAdapterBase):
 
     #: "float16" / "bfloat16": the clients' float32 entries arrive in 16 bits (None: float32 uploads)
     upload_dtype = None
+    #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
+    clip_noise_offset = 0
 
     def __init__(self, model: torch.nn.Module, optimizer=None, device=None, shards: Optional[ShardGroup] = None,
                  staging_capacity: Optional[int] = None, _load_from=None, dstream: Optional[DeviceStream] = None,
@@ -155,6 +157,9 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse("a sharded model or client-sharded ranks (ShardGroup)", self.upload_dtype)
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse("the q-fedavg server optimizer", self.upload_dtype)
+        #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
+        #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
+        self.clip_noise_offset = 0
         self.device = _resolve_device(device)
         if dstream is not None and dstream.device != self.device:
             raise ValueError(f"dstream is on {dstream.device}, the adapter on {self.device}")
@@ -208,9 +213,12 @@ class TorchModelAdapter(ModelAdapterBase):
     def _scratch_buffers(self):
         return self._f[1 - self._cur], self._s[1 - self._cur]
 
-    def _commit_scratch(self, host: Optional[_HostBuf] = None):
+    def _commit_scratch(self, host: Optional[_HostBuf] = None, rnd=None):
         """Make the scratch buffers the model.  ``host``: a pinned buffer the round's kernel is writing the new
-        model into (fa_reduce_mirror); it becomes the new version's egress snapshot, so egress needs no D2H."""
+        model into (fa_reduce_mirror); it becomes the new version's egress snapshot, so egress needs no D2H.
+        ``rnd``: the round being applied; a norm-clipped one moves the adapter's noise offset on."""
+        if getattr(rnd, "clip", None) is not None:
+            self.clip_noise_offset = rnd.next_noise_offset
         self._ready_stream = self.dstream.stream  # every write to the model buffers is issued on it
         self._ready.record(self._ready_stream)
         self._commit_ev = self._ready
@@ -470,12 +478,17 @@ class TorchModelAdapter(ModelAdapterBase):
 
     # ---- device fast path -----------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
-                    signatures: bool = False) -> DeviceRound:
+                    signatures: bool = False, clip=None) -> DeviceRound:
         """``keep_mean`` for q-FedAvg rounds: True fuses the FedAvg chain when the round spans several chunks
         (the staged updates are then gone by the end of the round), "always" in every round (the mean is then
         independent of the staging's later reuse), False never (model_weights of such rounds raises).
         ``signatures`` (FedAvg / FedBuff): the round also keeps every arrival's Auxo gradient signature against
-        the model it starts from (``DeviceRound.cohort_signatures``, fedscale_amd/cohort_signature.py)."""
+        the model it starts from (``DeviceRound.cohort_signatures``, fedscale_amd/cohort_signature.py).
+        ``clip`` (a ``clip_round.ClipSpec``; FedAvg rounds): every update is clipped to the spec's norm bound against
+        the model the round starts from, and the mean may carry Gaussian noise — a ``ClippedRound``
+        (fedscale_amd/clip_round.py)."""
+        if clip is not None:
+            self._check_clip(policy, signatures, clip)
         if self.upload_dtype is not None:
             return self._begin_half_round(K, policy, capacity, signatures)
         plan = None
@@ -502,11 +515,35 @@ class TorchModelAdapter(ModelAdapterBase):
             self.staging = None
             self.staging = ClientStaging(self.layout, self.device, want, dstream=self.dstream)
         snap = self._snapshot()
+        if clip is not None:
+            from ...clip_round import ClippedRound
+
+            return ClippedRound(self.layout, self.device, K, clip, staging=self.staging, last_f32=snap.f32,
+                                capacity=want, dstream=self.dstream, noise_offset=self.clip_noise_offset)
         chain = keep_mean == "always" or (bool(keep_mean) and want < K_local)
         return DeviceRound(self.layout, self.device, K, policy, capacity=want, staging=self.staging,
                            last_f32=snap.f32, last_i64=snap.side,
                            clients=self.shards if self.shards.shards_clients else None, mean_chain=chain,
                            dstream=self.dstream, signature_plan=plan)
+
+    def _check_clip(self, policy: str, signatures: bool, clip):
+        """Refuse, before a device is touched, what a norm-clipped round (``begin_round(clip=...)``) does not take."""
+        from ...clip_round import ClipSpec, refuse
+
+        if not isinstance(clip, ClipSpec):
+            raise TypeError(f"clip: expected a fedscale_amd.clip_round.ClipSpec, got {type(clip).__name__}")
+        if self.upload_dtype is not None:
+            raise refuse(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)")
+        if signatures:
+            raise refuse("cohort signatures")
+        if self.shards.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)")
+        if self.layout.world != 1:
+            raise refuse("a parameter-sharded layout")
+        if policy != "fedavg":
+            raise refuse(f"a {policy} round")
+        if self.optimizer is not None and getattr(self.optimizer, "mode", None) == "q-fedavg":
+            raise refuse("the q-fedavg server optimizer")
 
     def _begin_half_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool):
         """``begin_round`` of an adapter with ``upload_dtype``: a ``HalfRound`` over a ``HalfStaging`` whose default
@@ -597,9 +634,9 @@ class TorchModelAdapter(ModelAdapterBase):
                                   mirror=None if host is None else host.f)
             self._mean_f = out_f  # FedAvg without a server step: the mean IS the new model
             self._mean_valid = True
-            self._commit_scratch(host)
+            self._commit_scratch(host, rnd)
             return
-        self._commit_scratch()
+        self._commit_scratch(rnd=rnd)
 
     #: the small-round finish (``_finish_small``); False takes DeviceRound.finalize_mean for every round
     SMALL_ROUND_FINISH = True
@@ -614,6 +651,8 @@ class TorchModelAdapter(ModelAdapterBase):
         the round does not qualify (the caller takes finalize_mean)."""
         L = self.layout
         if self.upload_dtype is not None:  # a HalfRound has no pinned mirror of its rows
+            return False
+        if getattr(rnd, "clip", None) is not None:  # a ClippedRound finishes through fcl_finish
             return False
         if (not self.SMALL_ROUND_FINISH or host is None or L.Q or rnd.policy != "fedavg" or rnd.chunks_done
                 or rnd.cg is not None):
