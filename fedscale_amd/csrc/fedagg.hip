@@ -148,6 +148,14 @@ __device__ __forceinline__ float sgnf(float x) {  // torch.sign: -1, 0, +1 (NaN 
 }
 __device__ __forceinline__ double sgnd(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : x); }
 
+// A float32 value into an int64 state_dict entry, as load_state_dict's float32 -> int64 copy_ stores it on the
+// CPU: truncated toward zero, and INT64_MIN for what int64 cannot hold (NaN, +-inf, |v| >= 2^63; -2^63 is
+// INT64_MIN either way).  The bare cast is undefined on those inputs, and what gfx950 makes of it is another
+// value per class ("The side table").
+__device__ __forceinline__ int64_t f32_to_i64(float v) {
+  return (v > -9223372036854775808.f && v < 9223372036854775808.f) ? (int64_t)v : INT64_MIN;
+}
+
 // FedYoGi element step, op order of yogi.py:22-31 + optimizers.py:52-58 (fp32, every op rounded).
 __device__ __forceinline__ float yogi_elem(float cur, float last, float& m, float& v, float eta, float tau,
                                            float beta, float omb, float omb2) {
@@ -1972,7 +1980,7 @@ __global__ void k_side_close(const int64_t* acc_i, const double* acc_d, int Q, i
   if (q >= Q) return;
   const double c = (mode == 0 ? (double)acc_i[q] : acc_d[q]) / denom;
   if (cur) cur[q] = c;
-  if (model) model[q] = (int64_t)(float)c;  // np.asarray(float32) then float32 -> int64 copy (truncation)
+  if (model) model[q] = f32_to_i64((float)c);  // np.asarray(c, float32), then load_state_dict's copy_ into int64
 }
 
 extern "C" int fa_side_close(const int64_t* acc_i, const double* acc_d, int32_t Q, int32_t mode, double denom,
@@ -2005,7 +2013,7 @@ __global__ void k_side_yogi(const double* cur, const int64_t* last, double* m, d
   m[q] = M;
   v[q] = Vv;
   if (step) step[q] = st;
-  if (model) model[q] = (int64_t)(float)(L + st);  // np.array(last + diff, float32) -> load_state_dict
+  if (model) model[q] = f32_to_i64((float)(L + st));  // np.array(last + diff, float32) -> load_state_dict
 }
 
 extern "C" int fa_side_yogi(const double* cur, const int64_t* last, double* m, double* v, double* step,
@@ -2081,7 +2089,7 @@ __global__ void k_side_qfed_finalize(const int64_t* last, const float* delta_s, 
                                      int Q) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= Q) return;
-  model[q] = (int64_t)((float)last[q] - __fdiv_rn(delta_s[q], hs[1]));
+  model[q] = f32_to_i64((float)last[q] - __fdiv_rn(delta_s[q], hs[1]));
 }
 
 extern "C" int fa_side_qfed_finalize(const int64_t* last, const float* delta_s, const float* hs_dev, int64_t* model,

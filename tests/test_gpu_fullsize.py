@@ -113,6 +113,7 @@ def test_c4_fedyogi_k1000_p25m(gpu_device):
     from fedscale_amd import kernels as kx
     from fedscale_amd import synth
     from fedscale_amd.bucket import round_up
+    from tests.side_kernel_models import yogi_elem_f32
 
     K, P, seed = 1000, 25_000_000, 44
     ld = round_up(P, 64)
@@ -138,12 +139,7 @@ def test_c4_fedyogi_k1000_p25m(gpu_device):
         kx.reduce(x, K, P, mean_u, denom=float(f(K)), finalize=True)
         kx.yogi_step(mean_u, last_u, m_u, v_u, out_u, P, init=(r == 0), **hp)
         kx.reduce_yogi(x, K, P, last=last, m=m, v=v, out=out, denom=float(f(K)), init=(r == 0), mean_out=mean, **hp)
-        g = cur - L
-        g2 = g * g
-        mh = f(hp["beta"]) * mh + f(hp["omb"]) * g
-        vh = vh - (f(hp["omb2"]) * g2) * np.sign(vh - g2)
-        step = ((f(1) / (np.sqrt(vh) + f(hp["tau"]))) * f(hp["eta"])) * mh
-        new = L + step
+        mh, vh, new = yogi_elem_f32(cur, L, mh, vh, hp)  # yogi.py:22-31 in fp32, every operation rounded
         for got_mean, got_m, got_v, got_out in ((mean_u, m_u, v_u, out_u), (mean, m, v, out)):
             np.testing.assert_array_equal(got_mean[ci].cpu().numpy(), cur)
             np.testing.assert_array_equal(got_m[ci].cpu().numpy(), mh)
