@@ -107,6 +107,43 @@ _info = None
 _lock = threading.Lock()
 
 
+def bind(lib, signatures: dict, what: str) -> None:
+    """Type every symbol of a ``name -> (restype, argtypes)`` table onto ``lib``; ``what`` names the library in the
+    error of a missing symbol."""
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FedAggError(f"{what}: no symbol {name} (an older build; run `python __graft_entry__.py`)")
+        fn.restype = res
+        fn.argtypes = args
+
+
+def check_abi(lib, fn_name: str, want: int, what: str) -> None:
+    """The version ``fn_name()`` reports against ``want``; ``what`` opens the error ("<path>:", "<path>: fedhalf")."""
+    v = getattr(lib, fn_name)()
+    if v != want:
+        raise FedAggError(f"{what} ABI version {v}, expected {want}")
+
+
+def checked_call(lib, name: str, args, negative_only: bool = False):
+    """Call an entry point and return its code; raise with the library's last error string on a non-zero code, or
+    — ``negative_only``, for the functions that return counts — on a negative one."""
+    rc = getattr(lib, name)(*args)
+    if rc < 0 or (rc != 0 and not negative_only):
+        msg = lib.fa_last_error_string().decode(errors="replace")
+        raise FedAggError(f"{name} failed ({rc}): {msg}")
+    return rc
+
+
+def bind_header(signatures: dict, abi_fn: str, want: int, header: str):
+    """The library ``load()`` has verified, with one more header's table typed onto it and that header's ABI version
+    checked (the _native_* modules, once each)."""
+    lib = load()
+    bind(lib, signatures, LIB_PATH)
+    check_abi(lib, abi_fn, want, f"{LIB_PATH}: {header}")
+    return lib
+
+
 def check_build(lib, path: str, tree: str = None) -> dict:
     """The library's build id against the one the sources of ``tree`` (default: this checkout) produce with the
     library's own extra definitions (fedscale_amd/buildinfo.py); FedAggError on a mismatch — a library built
@@ -139,15 +176,8 @@ def load(path: str = None, tree: str = None):
             raise FedAggError(f"{path} not found: the HIP extension is not built "
                               f"(run `python __graft_entry__.py` to build it; there is no CPU fallback)")
         lib = ctypes.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name, None)
-            if fn is None:
-                raise FedAggError(f"{path}: no symbol {name} (an older build; run `python __graft_entry__.py`)")
-            fn.restype = res
-            fn.argtypes = args
-        v = lib.fa_abi_version()
-        if v != ABI_VERSION:
-            raise FedAggError(f"{path}: ABI version {v}, expected {ABI_VERSION}")
+        bind(lib, SIGNATURES, path)
+        check_abi(lib, "fa_abi_version", ABI_VERSION, f"{path}:")
         info = check_build(lib, path, tree)
         if os.environ.get("FEDAGG_STRICT_OPERANDS", "") not in ("", "0"):
             lib.fa_set_strict_operands(1)  # refuse device operands whose extent HIP cannot report (fa_device.h)
@@ -174,12 +204,7 @@ def operand_stats() -> dict:
 
 def call(name: str, *args):
     """Call an fa_* entry point; raise on a non-zero return code."""
-    lib = load()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.fa_last_error_string().decode(errors="replace")
-        raise FedAggError(f"{name} failed ({rc}): {msg}")
-    return rc
+    return checked_call(load(), name, args)
 
 
 def ptr(t) -> int:

@@ -7,10 +7,8 @@ a missing symbol or a failing call raises ``FedAggError``.
 from __future__ import annotations
 
 import ctypes
-import threading
 
 from . import _native
-from ._native import FedAggError
 
 ABI_VERSION = 1  # include/fedclip.h FCL_ABI_VERSION
 PLAN_FIELDS = 6  # FCL_PLAN_FIELDS
@@ -31,36 +29,16 @@ SIGNATURES = {
 }
 
 _lib = None
-_lock = threading.Lock()
 
 
 def load():
-    """The loaded library with the fcl_* entry points typed (once)."""
+    """The loaded library with the fcl_* entry points typed (once; a racing second typing sets the same types)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    lib = _native.load()
-    with _lock:
-        if _lib is None:
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name, None)
-                if fn is None:
-                    raise FedAggError(f"{_native.LIB_PATH}: no symbol {name} (an older build; run "
-                                      f"`python __graft_entry__.py`)")
-                fn.restype = res
-                fn.argtypes = args
-            v = lib.fcl_abi_version()
-            if v != ABI_VERSION:
-                raise FedAggError(f"{_native.LIB_PATH}: fedclip ABI version {v}, expected {ABI_VERSION}")
-            _lib = lib
+    if _lib is None:
+        _lib = _native.bind_header(SIGNATURES, "fcl_abi_version", ABI_VERSION, "fedclip")
     return _lib
 
 
 def call(name: str, *args):
     """Call an fcl_* entry point; raise on a negative return code (counts are returned)."""
-    lib = load()
-    rc = getattr(lib, name)(*args)
-    if rc < 0:
-        msg = lib.fa_last_error_string().decode(errors="replace")
-        raise FedAggError(f"{name} failed ({rc}): {msg}")
-    return rc
+    return _native.checked_call(load(), name, args, negative_only=True)

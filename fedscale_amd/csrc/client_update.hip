@@ -20,33 +20,13 @@
 
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/fedclient.h"
 #include "fa_device.h"
-
-// error plumbing shared with fedagg.hip (thread-local last-error string)
-extern "C" __attribute__((visibility("hidden"))) int fa_internal_set_error(int code, const char* msg);
+#include "fa_common.h"
 
 namespace {
-
-__attribute__((format(printf, 2, 3))) int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return fa_internal_set_error(code, buf);
-}
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(FA_E_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  return FA_OK;
-}
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int MT_MAX = 64;               // tensors per launch (kernel-argument table 2.8 KiB, < 4 KiB; `vec` is 64 bits)
 constexpr int MT_THREADS = 256;
@@ -233,11 +213,6 @@ __global__ __launch_bounds__(MT_THREADS) void k_sgd_prox(SgdList L, float c, int
 // ------------------------------------------------------------------------------------------------
 // max that propagates NaN, like torch.max (fmax would drop it)
 __device__ __forceinline__ double nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_xor(v, o, 64));

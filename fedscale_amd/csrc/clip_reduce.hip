@@ -11,63 +11,13 @@
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/fedclip.h"
 #include "fa_device.h"
+#include "fa_common.h"
 
 namespace {
-
-// an argument refused before the device scope opens: the same closing words as DevScope's operand errors
-__attribute__((format(printf, 2, 3))) int refuse(int code, const char* fmt, ...) {
-  char msg[400], buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(msg, sizeof(msg), fmt, ap);
-  va_end(ap);
-  snprintf(buf, sizeof(buf), "%s (nothing was launched)", msg);
-  return fa_internal_set_error(code, buf);
-}
-__attribute__((format(printf, 2, 3))) int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return fa_internal_set_error(code, buf);
-}
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(FA_E_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  return FA_OK;
-}
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-int cu_count() {
-  static int cache[64];  // per device ordinal (idempotent, benign race)
-  const int dev = fa_scope_device();
-  if (dev < 0 || dev >= 64) return 0;
-  if (cache[dev] > 0) return cache[dev];
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  cache[dev] = cus;
-  return cus;
-}
-
-// the 64 lanes' doubles added as a butterfly: every lane ends with the same sum (IEEE addition commutes), in an
-// order that is a function of the lane numbering alone
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------------
 // fcl_row_sqnorms
@@ -292,57 +242,23 @@ __global__ __launch_bounds__(64 * FCL_WAVES) void k_reduce_clip(ClipArgs r) {
   }
 }
 
-// Launch plan, in strips of 256 columns (S of them): fh_reduce's plan (reduce_half.hip) with fp32 rows.  Three
-// variants sized by registers — a lane holds 8V registers of `last` and chain plus 4UV of loads in flight:
+// Launch plan: strip_plan (fa_common.h) over strips of 256 columns, fh_reduce's plan with fp32 rows.  Its three
+// variants, sized by registers — a lane holds 8V registers of `last` and chain plus 4UV of loads in flight:
 //   level 0  V = 16, U = 1   128 + 64 registers, one wave per SIMD: the widest contiguous run per row (16 KiB)
 //   level 1  V =  8, U = 4    64 + 128 registers, two waves per SIMD
 //   level 2  V =  2, U = 8    16 +  64 registers: short rows need the parallelism
-// A bucket with at least 0.85 x cap level-0 tiles (cap = 75 % of the CUs) is ONE level-0 launch on a grid of at most
-// cap workgroups, each walking the same number of tiles, the last tile ragged.  A shorter bucket gives its whole
-// level-1 tiles to level 1 when they cover at least half the CUs, and what is left (all of it otherwise) to level 2.
 // K does not enter the plan today; it is a parameter because fa_reduce's plan depends on it.
-constexpr int FCL_NLEVELS = 3;
-constexpr int FCL_V[FCL_NLEVELS] = {16, 8, 2};
-constexpr int FCL_U[FCL_NLEVELS] = {1, 4, 8};
-constexpr int FCL_CAP_PCT = 75;
+constexpr StripGeo FCL_GEO{FCL_WAVES, {16, 8, 2}, {1, 4, 8}, 75, 256};
+static_assert(FCL_PLAN_FIELDS == STRIP_PLAN_FIELDS, "fcl_reduce_plan's row is strip_plan_export's");
 
-struct ClipLaunch {
-  int level;
-  int64_t strip0, tiles, grid;
-};
-
-int clip_plan(int64_t cus, int64_t P, ClipLaunch out[FCL_NLEVELS]) {
-  if (P <= 0 || cus <= 0) return 0;
-  const int64_t S = ((P + 3) / 4 + 63) / 64;
-  const int64_t cap = cus * FCL_CAP_PCT / 100 > 0 ? cus * FCL_CAP_PCT / 100 : 1;
-  const int64_t span0 = (int64_t)FCL_WAVES * FCL_V[0], span1 = (int64_t)FCL_WAVES * FCL_V[1],
-                span2 = (int64_t)FCL_WAVES * FCL_V[2];
-  const int64_t t0 = (S + span0 - 1) / span0;
-  if (t0 * 100 >= cap * 85) {
-    const int64_t rounds = (t0 + cap - 1) / cap;
-    out[0] = ClipLaunch{0, 0, t0, (t0 + rounds - 1) / rounds};
-    return 1;
-  }
-  int n = 0;
-  int64_t s = 0;
-  const int64_t n1 = S / span1;
-  if (n1 > 0 && 2 * n1 >= cus) {
-    out[n++] = ClipLaunch{1, 0, n1, n1};
-    s = n1 * span1;
-  }
-  if (s < S) {
-    const int64_t t2 = (S - s + span2 - 1) / span2;
-    out[n++] = ClipLaunch{2, s, t2, t2};
-  }
-  return n;
-}
+int64_t clip_strips(int64_t P) { return ((P + 3) / 4 + 63) / 64; }
 
 template <int V, int U>
-void launch_one(ClipArgs r, const ClipLaunch& l, hipStream_t st) {
+void launch_one(ClipArgs r, const StripLaunch& l, hipStream_t st) {
   r.c0 = l.strip0 * 64;
   r.ntiles = l.tiles;
   const dim3 grid((unsigned)l.grid), blk(64 * FCL_WAVES);
-  if constexpr (V == FCL_V[0]) {  // only level 0 runs on a capped grid
+  if constexpr (V == FCL_GEO.V[0]) {  // only level 0 runs on a capped grid
     if (l.grid < l.tiles) {
       hipLaunchKernelGGL((k_reduce_clip<V, U, true>), grid, blk, 0, st, r);
       return;
@@ -351,13 +267,13 @@ void launch_one(ClipArgs r, const ClipLaunch& l, hipStream_t st) {
   hipLaunchKernelGGL((k_reduce_clip<V, U, false>), grid, blk, 0, st, r);
 }
 
-void launch_level(const ClipArgs& r, const ClipLaunch& l, hipStream_t st) {
+void launch_level(const ClipArgs& r, const StripLaunch& l, hipStream_t st) {
   if (l.level == 0)
-    launch_one<FCL_V[0], FCL_U[0]>(r, l, st);
+    launch_one<FCL_GEO.V[0], FCL_GEO.U[0]>(r, l, st);
   else if (l.level == 1)
-    launch_one<FCL_V[1], FCL_U[1]>(r, l, st);
+    launch_one<FCL_GEO.V[1], FCL_GEO.U[1]>(r, l, st);
   else
-    launch_one<FCL_V[2], FCL_U[2]>(r, l, st);
+    launch_one<FCL_GEO.V[2], FCL_GEO.U[2]>(r, l, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -481,18 +397,7 @@ extern "C" int fcl_clip_coefs(const double* sq, int32_t n, double max_norm, floa
 extern "C" int64_t fcl_reduce_plan(int32_t cus, int32_t K, int64_t P, int64_t* plan_out, int32_t cap) {
   if (cus <= 0 || K < 0 || P < 0 || cap < 0 || (cap > 0 && !plan_out))
     return refuse(FA_E_ARG, "fcl_reduce_plan: bad arguments (cus=%d K=%d P=%lld cap=%d)", cus, K, (long long)P, cap);
-  ClipLaunch l[FCL_NLEVELS];
-  const int n = clip_plan(cus, P, l);
-  for (int i = 0; i < n && i < cap; ++i) {
-    int64_t* o = plan_out + (int64_t)FCL_PLAN_FIELDS * i;
-    o[0] = FCL_V[l[i].level];
-    o[1] = FCL_U[l[i].level];
-    o[2] = l[i].strip0 * 256;
-    o[3] = l[i].tiles;
-    o[4] = FCL_V[l[i].level];
-    o[5] = l[i].grid;
-  }
-  return n;
+  return strip_plan_export(cus, clip_strips(P), FCL_GEO, plan_out, cap);
 }
 
 extern "C" int fcl_reduce(const float* x, int64_t ld, int32_t n, int64_t P, const float* last, const float* c,
@@ -522,8 +427,8 @@ extern "C" int fcl_reduce(const float* x, int64_t ld, int32_t n, int64_t P, cons
   r.x = reinterpret_cast<const f4*>(x); r.ld4 = ld / 4; r.P4 = P4; r.P = P; r.n = n; r.flags = flags;
   r.last = reinterpret_cast<const f4*>(last); r.coef = c; r.acc_in = reinterpret_cast<const f4*>(acc_in);
   r.out = out;
-  ClipLaunch l[FCL_NLEVELS];
-  const int nl = clip_plan(cus, P, l);
+  StripLaunch l[3];
+  const int nl = strip_plan(cus, clip_strips(P), FCL_GEO, l);
   for (int i = 0; i < nl; ++i) {
     launch_level(r, l[i], (hipStream_t)stream);
     const int e = check_launch("fcl_reduce");

@@ -14,33 +14,17 @@
 
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/fedcohort.h"
 #include "fa_device.h"
+#include "fa_common.h"
 
 namespace {
-
-__attribute__((format(printf, 2, 3))) int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return fa_internal_set_error(code, buf);
-}
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(FA_E_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  return FA_OK;
-}
 
 typedef _Float16 h16;
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 
 // up to 8 float16 at p (the first nv are inside the matrix): one 16-byte load when `vec` and all 8 are valid
@@ -162,12 +146,6 @@ constexpr int CT_THREADS = 256;              // fc_normalize
 constexpr int64_t CT_COLS = CT_THREADS * 8;  // columns per workgroup (8 per thread: one 16-byte load per row)
 constexpr int CW_COLS = 64 * 8;              // fc_center: one wave per workgroup, 512 columns over all K rows
 constexpr int CT_SEG = 32;                   // first-level segments of the partial rows
-
-__device__ __forceinline__ double wave_sum(double v) {  // fixed butterfly: the same order on every run
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // part: [gridDim.x][K] fp64, one row per workgroup (= wave): its 512 columns of every client.  A wave walks the K
 // rows in order (the mean's chain is sequential in k), twice; the call's time follows K, not D.

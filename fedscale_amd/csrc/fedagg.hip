@@ -31,6 +31,7 @@
 
 #include "../../include/fedagg.h"
 #include "fa_device.h"
+#include "fa_common.h"
 
 // 2: fa_qfed_accumulate gained `chain`, fa_sgd_prox_step's dampening became double, and every launching
 //    entry point resolves its device from the stream / output pointer (fa_device.h)
@@ -56,26 +57,11 @@ __attribute__((used)) static const char fa_build_marker[] = "FA_BUILD_ID=" FA_BU
 #define FA_TUNING 0
 #endif
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------
-// error plumbing
+// error plumbing: the thread-local last-error string that fail() / refuse() (fa_common.h) and DevScope write
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 
-__attribute__((format(printf, 2, 3))) static int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-static int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(FA_E_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  return FA_OK;
-}
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // bytes a kernel touches in a client-major [K][ld] buffer of P columns (float4 columns past P included) and in
 // a per-column vector (operand extents for DevScope::operand)
 static uint64_t rows_bytes(int64_t K, int64_t ld, int64_t P, int elem = 4) {
@@ -83,7 +69,7 @@ static uint64_t rows_bytes(int64_t K, int64_t ld, int64_t P, int elem = 4) {
 }
 static uint64_t cols_bytes(int64_t P) { return (uint64_t)((P + 3) / 4) * 16; }
 
-// shared with the other translation units of the library (client_update.hip)
+// shared with the other translation units of the library
 extern "C" __attribute__((visibility("hidden"))) int fa_internal_set_error(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
   return code;
@@ -394,19 +380,6 @@ __global__ __launch_bounds__(64 * FA_RED_WAVES) void k_reduce(RedArgs r) {
 #ifndef FA_GRID_CAP_PCT
 #define FA_GRID_CAP_PCT 75  // concurrent V=32 workgroups as a percentage of the CU count
 #endif
-
-// CU count and occupancy of the device the running entry point works on (its DevScope), not the thread's
-// current device
-static int cu_count() {
-  static int cache[64];  // per device ordinal (idempotent, benign race)
-  const int dev = fa_scope_device();
-  if (dev < 0 || dev >= 64) return 0;
-  if (cache[dev] > 0) return cache[dev];
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  cache[dev] = cus;
-  return cus;
-}
 
 // fa_reduce_launches() runs the launch plan with g_plan_count set: every k_reduce launch site then counts
 // instead of launching, so the plan has one source of truth.

@@ -10,31 +10,14 @@
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/fedhalf.h"
 #include "fa_device.h"
+#include "fa_common.h"
 
 namespace {
 
-__attribute__((format(printf, 2, 3))) int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return fa_internal_set_error(code, buf);
-}
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(FA_E_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  return FA_OK;
-}
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
@@ -181,80 +164,30 @@ __global__ __launch_bounds__(64 * FH_WAVES) void k_reduce_half(HalfArgs r) {
   }
 }
 
-// Launch plan, in strips of 512 columns (S of them).  Three variants, sized by registers: one 16-byte load
-// becomes 8 fp32 accumulators, so a lane holds 8V + 4UV registers of data, and V x U KiB of loads are in flight
-// per wave (k_reduce's 32 KiB at the wide end):
+// Launch plan: strip_plan (fa_common.h) over strips of 512 columns.  Its three variants, sized by registers: one
+// 16-byte load becomes 8 fp32 accumulators, so a lane holds 8V + 4UV registers of data, and V x U KiB of loads are
+// in flight per wave (k_reduce's 32 KiB at the wide end):
 //   level 0  V = 16, U = 2   128 + 128 registers, one wave per SIMD: the widest contiguous run per row (16 KiB)
 //   level 1  V =  8, U = 4    64 + 128 registers, two waves per SIMD
 //   level 2  V =  2, U = 8    16 +  64 registers, five waves per SIMD: short rows need the parallelism
-// k_reduce's measurements carry over in their shape (profiles/r01_tune_grid_sweep.log: wide tiles on fewer
-// concurrent column streams read fastest): a bucket with at least 0.85 x cap level-0 tiles (cap = 75 % of the
-// CUs) is ONE level-0 launch on a grid of at most cap workgroups, each walking the same number of tiles, the last
-// tile ragged.  A shorter bucket gives its whole level-1 tiles to level 1 when they cover at least half the CUs,
-// and what is left (all of it otherwise) to level 2.  K and `weighted` do not enter the plan today; they are
-// parameters because fa_reduce's plan depends on them.
+// K and `weighted` do not enter the plan today; they are parameters because fa_reduce's plan depends on them.
 #ifndef FH_L2_V  // tuning knobs (tools/half_reduce_measure.py per library, FEDAGG_LIB): level 2's variant
 #define FH_L2_V 2
 #define FH_L2_U 8
 #elif !defined(FA_TUNING) || !FA_TUNING
 #error "FH_L2_V / FH_L2_U are tuning knobs: build with -DFA_TUNING=1"
 #endif
-constexpr int FH_NLEVELS = 3;
-constexpr int FH_V[FH_NLEVELS] = {16, 8, FH_L2_V};
-constexpr int FH_U[FH_NLEVELS] = {2, 4, FH_L2_U};
-constexpr int FH_CAP_PCT = 75;
+constexpr StripGeo FH_GEO{FH_WAVES, {16, 8, FH_L2_V}, {2, 4, FH_L2_U}, 75, 512};
+static_assert(FH_PLAN_FIELDS == STRIP_PLAN_FIELDS, "fh_reduce_plan's row is strip_plan_export's");
 
-struct HalfLaunch {
-  int level;
-  int64_t strip0, tiles, grid;
-};
-
-int half_plan(int64_t cus, int64_t P, HalfLaunch out[FH_NLEVELS]) {
-  if (P <= 0 || cus <= 0) return 0;
-  const int64_t S = ((P + 7) / 8 + 63) / 64;
-  const int64_t cap = cus * FH_CAP_PCT / 100 > 0 ? cus * FH_CAP_PCT / 100 : 1;
-  const int64_t span0 = (int64_t)FH_WAVES * FH_V[0], span1 = (int64_t)FH_WAVES * FH_V[1],
-                span2 = (int64_t)FH_WAVES * FH_V[2];
-  const int64_t t0 = (S + span0 - 1) / span0;
-  if (t0 * 100 >= cap * 85) {
-    const int64_t rounds = (t0 + cap - 1) / cap;
-    out[0] = HalfLaunch{0, 0, t0, (t0 + rounds - 1) / rounds};
-    return 1;
-  }
-  int n = 0;
-  int64_t s = 0;
-  const int64_t n1 = S / span1;
-  if (n1 > 0 && 2 * n1 >= cus) {
-    out[n++] = HalfLaunch{1, 0, n1, n1};
-    s = n1 * span1;
-  }
-  if (s < S) {
-    const int64_t t2 = (S - s + span2 - 1) / span2;
-    out[n++] = HalfLaunch{2, s, t2, t2};
-  }
-  return n;
-}
-
-int cu_count() {
-  static int cache[64];  // per device ordinal (idempotent, benign race)
-  const int dev = fa_scope_device();
-  if (dev < 0 || dev >= 64) return 0;
-  if (cache[dev] > 0) return cache[dev];
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  cache[dev] = cus;
-  return cus;
-}
+int64_t half_strips(int64_t P) { return ((P + 7) / 8 + 63) / 64; }
 
 template <int V, int U, bool BF, bool W>
-void launch_one(HalfArgs r, const HalfLaunch& l, hipStream_t st) {
+void launch_one(HalfArgs r, const StripLaunch& l, hipStream_t st) {
   r.c0 = l.strip0 * 64;
   r.ntiles = l.tiles;
   const dim3 grid((unsigned)l.grid), blk(64 * FH_WAVES);
-  if constexpr (V == FH_V[0]) {  // only level 0 runs on a capped grid
+  if constexpr (V == FH_GEO.V[0]) {  // only level 0 runs on a capped grid
     if (l.grid < l.tiles) {
       hipLaunchKernelGGL((k_reduce_half<V, U, BF, W, true>), grid, blk, 0, st, r);
       return;
@@ -264,13 +197,13 @@ void launch_one(HalfArgs r, const HalfLaunch& l, hipStream_t st) {
 }
 
 template <bool BF, bool W>
-void launch_level(const HalfArgs& r, const HalfLaunch& l, hipStream_t st) {
+void launch_level(const HalfArgs& r, const StripLaunch& l, hipStream_t st) {
   if (l.level == 0)
-    launch_one<FH_V[0], FH_U[0], BF, W>(r, l, st);
+    launch_one<FH_GEO.V[0], FH_GEO.U[0], BF, W>(r, l, st);
   else if (l.level == 1)
-    launch_one<FH_V[1], FH_U[1], BF, W>(r, l, st);
+    launch_one<FH_GEO.V[1], FH_GEO.U[1], BF, W>(r, l, st);
   else
-    launch_one<FH_V[2], FH_U[2], BF, W>(r, l, st);
+    launch_one<FH_GEO.V[2], FH_GEO.U[2], BF, W>(r, l, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -351,18 +284,7 @@ extern "C" int64_t fh_reduce_plan(int32_t cus, int32_t K, int64_t P, int32_t wei
   (void)weighted;
   if (cus <= 0 || K < 0 || P < 0 || cap < 0 || (cap > 0 && !plan_out))
     return fail(FA_E_ARG, "fh_reduce_plan: bad arguments (cus=%d K=%d P=%lld cap=%d)", cus, K, (long long)P, cap);
-  HalfLaunch l[FH_NLEVELS];
-  const int n = half_plan(cus, P, l);
-  for (int i = 0; i < n && i < cap; ++i) {
-    int64_t* o = plan_out + (int64_t)FH_PLAN_FIELDS * i;
-    o[0] = FH_V[l[i].level];
-    o[1] = FH_U[l[i].level];
-    o[2] = l[i].strip0 * 512;
-    o[3] = l[i].tiles;
-    o[4] = FH_V[l[i].level];
-    o[5] = l[i].grid;
-  }
-  return n;
+  return strip_plan_export(cus, half_strips(P), FH_GEO, plan_out, cap);
 }
 
 extern "C" int64_t fh_reduce_launches(int32_t K, int64_t P, int32_t weighted) {
@@ -370,8 +292,8 @@ extern "C" int64_t fh_reduce_launches(int32_t K, int64_t P, int32_t weighted) {
   if (K < 0 || P <= 0) return 0;
   const int cus = cu_count();
   if (cus <= 0) return fail(FA_E_HIP, "fh_reduce_launches: no CU count for device %d", fa_scope_device());
-  HalfLaunch l[FH_NLEVELS];
-  return half_plan(cus, P, l);
+  StripLaunch l[3];
+  return strip_plan(cus, half_strips(P), FH_GEO, l);
 }
 
 extern "C" int fh_reduce(const void* x16, int32_t row_dtype, int64_t ld, int32_t K, int64_t P, const float* a,
@@ -404,8 +326,8 @@ extern "C" int fh_reduce(const void* x16, int32_t row_dtype, int64_t ld, int32_t
   HalfArgs r{};
   r.x = reinterpret_cast<const u4*>(x16); r.ld8 = ld / 8; r.P8 = P8; r.P4 = P4; r.K = K; r.flags = flags;
   r.a = a; r.acc_in = acc_in; r.out = out; r.mirror = mirror; r.denom = denom;
-  HalfLaunch l[FH_NLEVELS];
-  const int n = half_plan(cus, P, l);
+  StripLaunch l[3];
+  const int n = strip_plan(cus, half_strips(P), FH_GEO, l);
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n; ++i) {
     if (row_dtype == FH_BF16) {

@@ -63,6 +63,17 @@ def _check_x(x: torch.Tensor, K: int, P: int, host_ok: bool = False):
     return ld
 
 
+def _strip_plan(plan_fn, fields: int) -> list:
+    """The launches a strip-plan export reports (fh_reduce_plan, fcl_reduce_plan): ``plan_fn(plan_out, cap)`` fills
+    rows of ``fields`` int64 and returns how many; a list of dicts V, U, col0, tiles, sw, grid."""
+    import numpy as np
+
+    buf = np.zeros(8 * fields, dtype=np.int64)
+    n = int(plan_fn(buf.ctypes.data, 8))
+    rows = buf[:n * fields].reshape(n, fields).tolist()
+    return [dict(zip(("V", "U", "col0", "tiles", "sw", "grid"), r)) for r in rows]
+
+
 def reduce(x: torch.Tensor, K: int, P: int, out: torch.Tensor, *, a: Optional[torch.Tensor] = None,
            acc_in: Optional[torch.Tensor] = None, denom: float = 1.0, finalize: bool = False,
            host_ok: bool = False) -> torch.Tensor:

@@ -10,7 +10,7 @@ import torch
 
 from . import _native_clip as NC
 from ._native import FA_ACCUMULATE, ptr
-from .kernels import _check_x, _cols, _dev, _pinned, _stream
+from .kernels import _check_x, _cols, _dev, _pinned, _stream, _strip_plan
 
 
 def workspace_bytes(n: int, P: int) -> int:
@@ -70,10 +70,8 @@ def reduce_clip(x: torch.Tensor, n: int, P: int, last: torch.Tensor, c: torch.Te
 def reduce_clip_plan(cus: int, K: int, P: int) -> list:
     """The launches fcl_reduce makes at (K, P) on a GPU of ``cus`` compute units (fcl_reduce_plan; no GPU needed):
     a list of dicts V, U, col0, tiles, sw, grid."""
-    buf = np.zeros(8 * NC.PLAN_FIELDS, dtype=np.int64)
-    n = int(NC.call("fcl_reduce_plan", int(cus), int(K), int(P), buf.ctypes.data, 8))
-    rows = buf[:n * NC.PLAN_FIELDS].reshape(n, NC.PLAN_FIELDS).tolist()
-    return [dict(zip(("V", "U", "col0", "tiles", "sw", "grid"), r)) for r in rows]
+    return _strip_plan(lambda out, cap: NC.call("fcl_reduce_plan", int(cus), int(K), int(P), out, cap),
+                       NC.PLAN_FIELDS)
 
 
 def finish(chain: torch.Tensor, last: torch.Tensor, P: int, denom: float, out: torch.Tensor, *,

@@ -11,7 +11,7 @@ import torch
 
 from . import _native_half as NH
 from ._native import FA_ACCUMULATE, FA_FINALIZE, ptr
-from .kernels import _cols, _dev, _pinned, _stream
+from .kernels import _cols, _dev, _pinned, _stream, _strip_plan
 
 #: the 16-bit row element types: name -> (torch dtype, FH_* code)
 ROW_DTYPES = {"float16": (torch.float16, NH.FH_F16), "bfloat16": (torch.bfloat16, NH.FH_BF16)}
@@ -73,10 +73,8 @@ def reduce16(x16: torch.Tensor, K: int, P: int, out: torch.Tensor, *, a: Optiona
 def reduce16_plan(cus: int, K: int, P: int, weighted: bool = False) -> list:
     """The launches fh_reduce makes at (K, P) on a GPU of ``cus`` compute units (fh_reduce_plan; no GPU needed):
     a list of dicts V, U, col0, tiles, sw, grid."""
-    buf = np.zeros(8 * NH.PLAN_FIELDS, dtype=np.int64)
-    n = int(NH.call("fh_reduce_plan", int(cus), int(K), int(P), 1 if weighted else 0, buf.ctypes.data, 8))
-    rows = buf[:n * NH.PLAN_FIELDS].reshape(n, NH.PLAN_FIELDS).tolist()
-    return [dict(zip(("V", "U", "col0", "tiles", "sw", "grid"), r)) for r in rows]
+    return _strip_plan(lambda out, cap: NH.call("fh_reduce_plan", int(cus), int(K), int(P), 1 if weighted else 0,
+                                                out, cap), NH.PLAN_FIELDS)
 
 
 def reduce16_launches(K: int, P: int, weighted: bool = False) -> int:

@@ -1,7 +1,7 @@
 """Shared by the norm-clipped aggregation tests: the arithmetic of include/fedclip.h restated in numpy (with
 ``math.fsum`` for the exact squared norm), ``fcl_reduce``'s and ``fcl_row_sqnorms``' launch plans restated in Python
-(clip_plan / norm_tiles / norm_grid of fedscale_amd/csrc/clip_reduce.hip), and the shapes the GPU tests run as a
-function of the CU count, with the plan each is meant to hit."""
+(strip_plan of fedscale_amd/csrc/fa_common.h with FCL_GEO, norm_tiles / norm_grid of clip_reduce.hip), and the
+shapes the GPU tests run as a function of the CU count, with the plan each is meant to hit."""
 import math
 
 import numpy as np

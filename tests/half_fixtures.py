@@ -1,6 +1,6 @@
-"""Shared by the 16-bit upload tests: ``fh_reduce``'s launch plan restated in Python (half_plan of
-fedscale_amd/csrc/reduce_half.hip), the shapes the GPU tests run as a function of the CU count, with the plan each
-is meant to hit, and exact widening of 16-bit arrays on the host."""
+"""Shared by the 16-bit upload tests: ``fh_reduce``'s launch plan restated in Python (strip_plan of
+fedscale_amd/csrc/fa_common.h with FH_GEO of reduce_half.hip), the shapes the GPU tests run as a function of the CU
+count, with the plan each is meant to hit, and exact widening of 16-bit arrays on the host."""
 import numpy as np
 
 # constants of reduce_half.hip
