@@ -95,6 +95,12 @@ class DeviceAggregatorMixin:
     device_clip_noise_multiplier = 0.0
     #: seed of that noise stream
     device_clip_seed = 0
+    #: opt-in: the coordinate-wise trimmed mean — for every parameter the t smallest and t largest of the K uploaded
+    #: values are dropped on the device and the rest averaged (fedscale_amd/trim_round.py; INTEGRATION.md,
+    #: "Trimmed-mean aggregation").  An int: t per side; a float in [0, 0.5): the fraction per side; "median".
+    #: FedAvg and fed-yogi; q-FedAvg, device_clip_norm, device_shards, device_upload_dtype, the async and the cohort
+    #: mixin are refused with it
+    device_trim = None
 
     _device_round = None
 
@@ -105,6 +111,22 @@ class DeviceAggregatorMixin:
         from ...clip_round import ClipSpec
 
         return ClipSpec(self.device_clip_norm, self.device_clip_noise_multiplier, self.device_clip_seed)
+
+    def _trim_spec(self):
+        """The ``TrimSpec`` of this aggregator's rounds (None: ``device_trim`` is not set), after refusing the
+        attributes it does not combine with."""
+        if self.device_trim is None:
+            return None
+        from ...trim_round import TrimSpec, refuse
+
+        spec = TrimSpec(self.device_trim)
+        if self.device_clip_norm is not None:
+            raise refuse("device_clip_norm (a norm-clipped round)")
+        if self.device_upload_dtype is not None:
+            raise refuse(f"device_upload_dtype={self.device_upload_dtype!r} (16-bit uploads)")
+        if self.device_shards is not None and len(self.device_shards) > 1:
+            raise refuse("device_shards (a model sharded over several GPUs)")
+        return spec
 
     # same predicates as aggregator.py:430-434 (defined here too so the mixin also works standalone)
     def _is_first_result_in_round(self):
@@ -292,6 +314,9 @@ class DeviceAggregatorMixin:
             w = self._wrapper()
             clip = self._clip_spec()
             kw = {} if clip is None else {"clip": clip}  # (unset, the call is what it was)
+            trim = self._trim_spec()
+            if trim is not None:
+                kw["trim"] = trim
             rnd = self._device_round = w.begin_round(self.tasks_round, self._device_policy(),
                                                      capacity=self.device_round_capacity,
                                                      keep_mean=self.device_keep_mean, **kw)
@@ -319,6 +344,10 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
     def update_weight_aggregation(self, results):
         if self.device_clip_norm is not None:
             from ...clip_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
+        if self.device_trim is not None:
+            from ...trim_round import refuse
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         w = self._wrapper()
@@ -360,6 +389,10 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
     def update_weight_aggregation(self, results, cohort_id=0):
         if self.device_clip_norm is not None:
             from ...clip_round import refuse
+
+            raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
+        if self.device_trim is not None:
+            from ...trim_round import refuse
 
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         w = self.model_wrapper[cohort_id]

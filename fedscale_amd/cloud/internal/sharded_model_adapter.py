@@ -234,7 +234,11 @@ class ShardedModelAdapter(TorchModelAdapter):
 
     # ---- rounds -----------------------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
-                    signatures: bool = False, clip=None) -> ShardedRound:
+                    signatures: bool = False, clip=None, trim=None) -> ShardedRound:
+        if trim is not None:  # trimmed rounds (fedscale_amd/trim_round.py): one whole model on one device
+            from ...trim_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)")
         if clip is not None:  # norm-clipped rounds (fedscale_amd/clip_round.py): one whole model on one device
             from ...clip_round import refuse
 

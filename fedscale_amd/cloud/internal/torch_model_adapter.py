@@ -478,7 +478,7 @@ class TorchModelAdapter(ModelAdapterBase):
 
     # ---- device fast path -----------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
-                    signatures: bool = False, clip=None) -> DeviceRound:
+                    signatures: bool = False, clip=None, trim=None) -> DeviceRound:
         """``keep_mean`` for q-FedAvg rounds: True fuses the FedAvg chain when the round spans several chunks
         (the staged updates are then gone by the end of the round), "always" in every round (the mean is then
         independent of the staging's later reuse), False never (model_weights of such rounds raises).
@@ -486,7 +486,13 @@ class TorchModelAdapter(ModelAdapterBase):
         the model it starts from (``DeviceRound.cohort_signatures``, fedscale_amd/cohort_signature.py).
         ``clip`` (a ``clip_round.ClipSpec``; FedAvg rounds): every update is clipped to the spec's norm bound against
         the model the round starts from, and the mean may carry Gaussian noise — a ``ClippedRound``
-        (fedscale_amd/clip_round.py)."""
+        (fedscale_amd/clip_round.py).
+        ``trim`` (a ``trim_round.TrimSpec``, or what it takes: a count, a fraction or "median"; FedAvg rounds): for
+        every parameter the t smallest and t largest uploaded values are dropped and the rest averaged — a
+        ``TrimmedRound`` (fedscale_amd/trim_round.py), which needs all K uploads resident."""
+        if trim is not None:
+            trim = self._check_trim(policy, signatures, clip, trim)
+            trim.count(K)  # (a count the round cannot take is refused here, with nothing allocated)
         if clip is not None:
             self._check_clip(policy, signatures, clip)
         if self.upload_dtype is not None:
@@ -511,9 +517,17 @@ class TorchModelAdapter(ModelAdapterBase):
             want = min(default_capacity(self.layout, K_local, self.device), K_local)
         if policy == "qfedavg":  # phase-1 chunks hold at most fa_qfed_max_chunk() clients
             want = min(want, kx_qfed_max_chunk())
+        if trim is not None and want < K:  # before the staging is (re)allocated, and before any launch
+            raise ValueError(f"a trimmed round needs all K={K} uploads resident, the staging capacity is {want}: "
+                             f"there is no chunk folding (raise capacity=, or lower K)")
         if self.staging is None or self.staging.capacity < want:
             self.staging = None
             self.staging = ClientStaging(self.layout, self.device, want, dstream=self.dstream)
+        if trim is not None:
+            from ...trim_round import TrimmedRound
+
+            return TrimmedRound(self.layout, self.device, K, trim, staging=self.staging, capacity=want,
+                                dstream=self.dstream)
         snap = self._snapshot()
         if clip is not None:
             from ...clip_round import ClippedRound
@@ -544,6 +558,28 @@ class TorchModelAdapter(ModelAdapterBase):
             raise refuse(f"a {policy} round")
         if self.optimizer is not None and getattr(self.optimizer, "mode", None) == "q-fedavg":
             raise refuse("the q-fedavg server optimizer")
+
+    def _check_trim(self, policy: str, signatures: bool, clip, trim):
+        """Refuse, before a device is touched, what a trimmed round (``begin_round(trim=...)``) does not take; the
+        ``TrimSpec`` of ``trim``."""
+        from ...trim_round import TrimSpec, refuse
+
+        spec = TrimSpec(trim)
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)")
+        if self.upload_dtype is not None:
+            raise refuse(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)")
+        if signatures:
+            raise refuse("cohort signatures")
+        if self.shards.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)")
+        if self.layout.world != 1:
+            raise refuse("a parameter-sharded layout")
+        if policy != "fedavg":
+            raise refuse(f"a {policy} round")
+        if self.optimizer is not None and getattr(self.optimizer, "mode", None) == "q-fedavg":
+            raise refuse("the q-fedavg server optimizer")
+        return spec
 
     def _begin_half_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool):
         """``begin_round`` of an adapter with ``upload_dtype``: a ``HalfRound`` over a ``HalfStaging`` whose default
@@ -653,6 +689,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if self.upload_dtype is not None:  # a HalfRound has no pinned mirror of its rows
             return False
         if getattr(rnd, "clip", None) is not None:  # a ClippedRound finishes through fcl_finish
+            return False
+        if getattr(rnd, "trim", None) is not None:  # a TrimmedRound finishes through ft_reduce
             return False
         if (not self.SMALL_ROUND_FINISH or host is None or L.Q or rnd.policy != "fedavg" or rnd.chunks_done
                 or rnd.cg is not None):
