@@ -81,11 +81,16 @@ class ShardedModelAdapter(TorchModelAdapter):
     REGISTER_MAX_PENDING = 4
 
     def __init__(self, model: torch.nn.Module, optimizer=None, devices=None, staging_capacity: Optional[int] = None,
-                 transport: Optional[str] = None, upload_dtype: Optional[str] = None):
+                 transport: Optional[str] = None, upload_dtype: Optional[str] = None,
+                 upload_quant: Optional[str] = None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_dtype)
+        if upload_quant is not None:  # MXFP8 delta uploads (fedscale_amd/quant_round.py): likewise
+            from ...quant_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_quant)
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -136,15 +136,20 @@ class TorchModelAdapter(ModelAdapterBase):
 
     #: "float16" / "bfloat16": the clients' float32 entries arrive in 16 bits (None: float32 uploads)
     upload_dtype = None
+    #: "mxfp8": the clients upload MXFP8-quantised deltas against the round's model (None: whole weights)
+    upload_quant = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
     def __init__(self, model: torch.nn.Module, optimizer=None, device=None, shards: Optional[ShardGroup] = None,
                  staging_capacity: Optional[int] = None, _load_from=None, dstream: Optional[DeviceStream] = None,
-                 upload_dtype: Optional[str] = None):
+                 upload_dtype: Optional[str] = None, upload_quant: Optional[str] = None):
         """``upload_dtype`` ("float16" / "bfloat16"; None: float32 uploads, as the reference's): clients upload
         their float32 entries in 16 bits (fedscale_amd/cloud/execution/half_upload.py); ``begin_round`` then
-        returns a ``HalfRound`` over a ``HalfStaging`` (fedscale_amd/half_round.py)."""
+        returns a ``HalfRound`` over a ``HalfStaging`` (fedscale_amd/half_round.py).
+        ``upload_quant`` ("mxfp8"; None: whole weights): clients upload their update against the weights they were
+        sent for this round, quantised to MXFP8 (fedscale_amd/cloud/execution/quant_upload.py); ``begin_round`` then
+        returns a ``QuantRound`` over a ``QuantStaging`` (fedscale_amd/quant_round.py)."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -157,6 +162,18 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse("a sharded model or client-sharded ranks (ShardGroup)", self.upload_dtype)
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse("the q-fedavg server optimizer", self.upload_dtype)
+        self.upload_quant = None
+        if upload_quant is not None:
+            from ...quant_round import check_format
+            from ...quant_round import refuse as refuse_q
+
+            self.upload_quant = check_format(upload_quant)
+            if self.upload_dtype is not None:
+                raise refuse_q(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)")
+            if shards is not None and shards.world != 1:
+                raise refuse_q("a sharded model or client-sharded ranks (ShardGroup)")
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse_q("the q-fedavg server optimizer")
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -472,6 +489,9 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if self.upload_quant is not None:
+            return (self.__class__, (self.get_model(), self.optimizer, None, None, None, None, None, self.upload_dtype,
+                                     self.upload_quant))
         if self.upload_dtype is not None:
             return (self.__class__, (self.get_model(), self.optimizer, None, None, None, None, None, self.upload_dtype))
         return (self.__class__, (self.get_model(), self.optimizer))
@@ -490,6 +510,8 @@ class TorchModelAdapter(ModelAdapterBase):
         ``trim`` (a ``trim_round.TrimSpec``, or what it takes: a count, a fraction or "median"; FedAvg rounds): for
         every parameter the t smallest and t largest uploaded values are dropped and the rest averaged — a
         ``TrimmedRound`` (fedscale_amd/trim_round.py), which needs all K uploads resident."""
+        if getattr(self, "upload_quant", None) is not None:
+            return self._begin_quant_round(K, policy, capacity, signatures, clip, trim)
         if trim is not None:
             trim = self._check_trim(policy, signatures, clip, trim)
             trim.count(K)  # (a count the round cannot take is refused here, with nothing allocated)
@@ -603,6 +625,35 @@ class TorchModelAdapter(ModelAdapterBase):
         return HalfRound(self.layout, self.device, K, policy, staging=self.staging, capacity=want,
                          dstream=self.dstream)
 
+    def _begin_quant_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim):
+        """``begin_round`` of an adapter with ``upload_quant``: a ``QuantRound`` over a ``QuantStaging`` whose default
+        capacity is computed from rows of 1 + 1/32 bytes per parameter.  The combinations the quantised-delta path
+        does not take are refused here, before a device is touched."""
+        from ...quant_round import QuantRound, QuantStaging, default_capacity8, refuse
+
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)", self.upload_quant)
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)", self.upload_quant)
+        if signatures:
+            raise refuse("cohort signatures", self.upload_quant)
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round", self.upload_quant)
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)", self.upload_quant)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            want = default_capacity8(self.layout, K, self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = QuantStaging(self.layout, self.device, want, dstream=self.dstream)
+        return QuantRound(self.layout, self.device, K, policy, staging=self.staging, last_f32=self._snapshot().f32,
+                          capacity=want, dstream=self.dstream)
+
     def apply_round(self, rnd: DeviceRound, denom32: float, denom64: float, client_training_results=None,
                     keep_mean: bool = True):
         """Finish a round: reduce the last chunk with the server step fused, then swap buffers."""
@@ -687,6 +738,8 @@ class TorchModelAdapter(ModelAdapterBase):
         the round does not qualify (the caller takes finalize_mean)."""
         L = self.layout
         if self.upload_dtype is not None:  # a HalfRound has no pinned mirror of its rows
+            return False
+        if getattr(rnd, "upload_quant", None) is not None:  # a QuantRound finishes through fcl_finish
             return False
         if getattr(rnd, "clip", None) is not None:  # a ClippedRound finishes through fcl_finish
             return False
