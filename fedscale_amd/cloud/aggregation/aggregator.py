@@ -92,6 +92,13 @@ class DeviceAggregatorMixin:
     #: fed-yogi; q-FedAvg, device_shards, device_upload_dtype, device_clip_norm, device_trim, the async and the cohort
     #: mixin's signatures are refused with it
     device_upload_quant = None
+    #: opt-in: a density in (0, 1] — the executors upload the ceil(density * P) largest-magnitude entries of their
+    #: update against the weights they were sent for this round, as (index, value) pairs
+    #: (fedscale_amd/cloud/execution/sparse_upload.py: lossy on the wire, exact from there on; error feedback is the
+    #: executor's state); staged in HBM at 8 bytes per kept entry and chained in fp32 (fedscale_amd/sparse_round.py).
+    #: FedAvg and fed-yogi; q-FedAvg, device_shards, device_upload_dtype, device_upload_quant, device_clip_norm,
+    #: device_trim, the async and the cohort mixin's signatures are refused with it
+    device_upload_topk = None
     #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
     #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
     #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
@@ -178,6 +185,8 @@ class DeviceAggregatorMixin:
             kw = {} if self.device_upload_dtype is None else {"upload_dtype": self.device_upload_dtype}
             if self.device_upload_quant is not None:
                 kw["upload_quant"] = self.device_upload_quant
+            if self.device_upload_topk is not None:
+                kw["upload_topk"] = self.device_upload_topk
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
         else:
             dev = devs[0] if devs else self._aggregation_device()
@@ -185,6 +194,8 @@ class DeviceAggregatorMixin:
             kw = {} if self.device_upload_dtype is None else {"upload_dtype": self.device_upload_dtype}
             if self.device_upload_quant is not None:
                 kw["upload_quant"] = self.device_upload_quant
+            if self.device_upload_topk is not None:
+                kw["upload_topk"] = self.device_upload_topk
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
             if self.device_numa_bind:
                 from ...hostnuma import bind_to_gpu
@@ -365,6 +376,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_quant)
+        if self.device_upload_topk is not None:
+            from ...sparse_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
+                         self.device_upload_topk)
         w = self._wrapper()
         # async_aggregator.py:125-126 — Python-float weight and denominator
         s = 1 / (1 + self.round - self.client_task_model_version[results["client_id"]]) ** 0.5

@@ -82,7 +82,7 @@ class ShardedModelAdapter(TorchModelAdapter):
 
     def __init__(self, model: torch.nn.Module, optimizer=None, devices=None, staging_capacity: Optional[int] = None,
                  transport: Optional[str] = None, upload_dtype: Optional[str] = None,
-                 upload_quant: Optional[str] = None):
+                 upload_quant: Optional[str] = None, upload_topk: Optional[float] = None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
@@ -91,6 +91,10 @@ class ShardedModelAdapter(TorchModelAdapter):
             from ...quant_round import refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_quant)
+        if upload_topk is not None:  # top-k sparse delta uploads (fedscale_amd/sparse_round.py): likewise
+            from ...sparse_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_topk)
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -17,6 +17,7 @@ Device fast path used by ``DeviceAggregatorMixin``:
 """
 from __future__ import annotations
 
+import functools
 import itertools
 import threading
 from typing import List, Optional
@@ -126,6 +127,28 @@ def _resolve_device(device) -> torch.device:
     return d
 
 
+def _takes_upload_topk(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_topk``.  The constructor's own
+    parameter list is the positional layout ``__reduce__`` pickles a dense, 16-bit or MXFP8 adapter by, and stays
+    what it is; the option is set on the instance before the constructor's body runs (which refuses what it does not
+    combine with), and an adapter that has it pickles through ``_rebuild_with_upload_topk``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_topk: Optional[float] = None, **kw):
+        if upload_topk is not None:
+            from ...sparse_round import check_density
+
+            self.upload_topk = check_density(upload_topk)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_topk(cls, model, optimizer, density):
+    """Unpickle an adapter with ``upload_topk`` (``TorchModelAdapter.__reduce__``)."""
+    return cls(model, optimizer, upload_topk=density)
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -138,9 +161,12 @@ class TorchModelAdapter(ModelAdapterBase):
     upload_dtype = None
     #: "mxfp8": the clients upload MXFP8-quantised deltas against the round's model (None: whole weights)
     upload_quant = None
+    #: a density in (0, 1]: the clients upload top-k sparse deltas against the round's model (None: whole weights)
+    upload_topk = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_topk
     def __init__(self, model: torch.nn.Module, optimizer=None, device=None, shards: Optional[ShardGroup] = None,
                  staging_capacity: Optional[int] = None, _load_from=None, dstream: Optional[DeviceStream] = None,
                  upload_dtype: Optional[str] = None, upload_quant: Optional[str] = None):
@@ -149,7 +175,12 @@ class TorchModelAdapter(ModelAdapterBase):
         returns a ``HalfRound`` over a ``HalfStaging`` (fedscale_amd/half_round.py).
         ``upload_quant`` ("mxfp8"; None: whole weights): clients upload their update against the weights they were
         sent for this round, quantised to MXFP8 (fedscale_amd/cloud/execution/quant_upload.py); ``begin_round`` then
-        returns a ``QuantRound`` over a ``QuantStaging`` (fedscale_amd/quant_round.py)."""
+        returns a ``QuantRound`` over a ``QuantStaging`` (fedscale_amd/quant_round.py).
+        ``upload_topk`` (keyword only, taken by ``_takes_upload_topk`` below; a density in (0, 1]; None: whole
+        weights): clients upload the largest-magnitude ``ceil(density * P)`` entries of their update against the
+        weights they were sent for this round, as (index, value) pairs
+        (fedscale_amd/cloud/execution/sparse_upload.py); ``begin_round`` then returns a ``SparseRound`` over a
+        ``SparseStaging`` (fedscale_amd/sparse_round.py)."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -174,6 +205,18 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse_q("a sharded model or client-sharded ranks (ShardGroup)")
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse_q("the q-fedavg server optimizer")
+        topk = self.__dict__.get("upload_topk")  # set by _takes_upload_topk before this body runs
+        if topk is not None:
+            from ...sparse_round import refuse as refuse_s
+
+            if self.upload_dtype is not None:
+                raise refuse_s(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)", topk)
+            if self.upload_quant is not None:
+                raise refuse_s(f"upload_quant={self.upload_quant!r} (MXFP8 delta uploads)", topk)
+            if shards is not None and shards.world != 1:
+                raise refuse_s("a sharded model or client-sharded ranks (ShardGroup)", topk)
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse_s("the q-fedavg server optimizer", topk)
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -489,6 +532,8 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if getattr(self, "upload_topk", None) is not None:
+            return (_rebuild_with_upload_topk, (self.__class__, self.get_model(), self.optimizer, self.upload_topk))
         if self.upload_quant is not None:
             return (self.__class__, (self.get_model(), self.optimizer, None, None, None, None, None, self.upload_dtype,
                                      self.upload_quant))
@@ -510,6 +555,8 @@ class TorchModelAdapter(ModelAdapterBase):
         ``trim`` (a ``trim_round.TrimSpec``, or what it takes: a count, a fraction or "median"; FedAvg rounds): for
         every parameter the t smallest and t largest uploaded values are dropped and the rest averaged — a
         ``TrimmedRound`` (fedscale_amd/trim_round.py), which needs all K uploads resident."""
+        if getattr(self, "upload_topk", None) is not None:
+            return self._begin_sparse_round(K, policy, capacity, signatures, clip, trim)
         if getattr(self, "upload_quant", None) is not None:
             return self._begin_quant_round(K, policy, capacity, signatures, clip, trim)
         if trim is not None:
@@ -654,6 +701,39 @@ class TorchModelAdapter(ModelAdapterBase):
         return QuantRound(self.layout, self.device, K, policy, staging=self.staging, last_f32=self._snapshot().f32,
                           capacity=want, dstream=self.dstream)
 
+    def _begin_sparse_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim):
+        """``begin_round`` of an adapter with ``upload_topk``: a ``SparseRound`` over a ``SparseStaging`` whose rows
+        hold the ``ceil(density * P)`` pairs the declared density keeps.  The combinations the sparse-delta path does
+        not take are refused here, before a device is touched."""
+        from ...sparse_round import SparseRound, SparseStaging, default_capacity_topk, refuse
+
+        d = self.upload_topk
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)", d)
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)", d)
+        if signatures:
+            raise refuse("cohort signatures", d)
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round", d)
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)", d)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            from ..execution.sparse_upload import count_of
+
+            kmax = count_of(d, self.layout.P) if self.layout.P else 0
+            want = default_capacity_topk(self.layout, K, kmax, self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = SparseStaging(self.layout, self.device, want, d, dstream=self.dstream)
+        return SparseRound(self.layout, self.device, K, policy, staging=self.staging, last_f32=self._snapshot().f32,
+                           capacity=want, dstream=self.dstream)
+
     def apply_round(self, rnd: DeviceRound, denom32: float, denom64: float, client_training_results=None,
                     keep_mean: bool = True):
         """Finish a round: reduce the last chunk with the server step fused, then swap buffers."""
@@ -740,6 +820,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if self.upload_dtype is not None:  # a HalfRound has no pinned mirror of its rows
             return False
         if getattr(rnd, "upload_quant", None) is not None:  # a QuantRound finishes through fcl_finish
+            return False
+        if getattr(rnd, "upload_topk", None) is not None:  # a SparseRound finishes through fcl_finish
             return False
         if getattr(rnd, "clip", None) is not None:  # a ClippedRound finishes through fcl_finish
             return False
