@@ -114,6 +114,13 @@ class DeviceAggregatorMixin:
     #: FedAvg and fed-yogi; q-FedAvg, device_clip_norm, device_shards, device_upload_dtype, the async and the cohort
     #: mixin are refused with it
     device_trim = None
+    #: opt-in: Krum / Multi-Krum — every upload is scored by its squared distance to its K - f - 2 nearest other
+    #: uploads on the device and only the m best-scored uploads are averaged (fedscale_amd/krum_round.py;
+    #: INTEGRATION.md, "Multi-Krum aggregation").  An f (int, or a fraction in [0, 0.5)): Multi-Krum, m = K - f; an
+    #: (f, m) pair (m = 1: Krum); or a KrumSpec.  FedAvg and fed-yogi; q-FedAvg, device_clip_norm, device_trim,
+    #: device_shards, device_upload_dtype, device_upload_quant, device_upload_topk, the async and the cohort mixin
+    #: are refused with it
+    device_krum = None
 
     _device_round = None
 
@@ -137,6 +144,29 @@ class DeviceAggregatorMixin:
             raise refuse("device_clip_norm (a norm-clipped round)")
         if self.device_upload_dtype is not None:
             raise refuse(f"device_upload_dtype={self.device_upload_dtype!r} (16-bit uploads)")
+        if self.device_shards is not None and len(self.device_shards) > 1:
+            raise refuse("device_shards (a model sharded over several GPUs)")
+        return spec
+
+    def _krum_spec(self):
+        """The ``KrumSpec`` of this aggregator's rounds (None: ``device_krum`` is not set), after refusing the
+        attributes it does not combine with."""
+        k = self.device_krum
+        if k is None:
+            return None
+        from ...krum_round import KrumSpec, refuse
+
+        spec = KrumSpec(*k) if isinstance(k, (tuple, list)) and len(k) == 2 else KrumSpec(k)
+        if self.device_clip_norm is not None:
+            raise refuse("device_clip_norm (a norm-clipped round)")
+        if self.device_trim is not None:
+            raise refuse("device_trim (a trimmed-mean round)")
+        if self.device_upload_dtype is not None:
+            raise refuse(f"device_upload_dtype={self.device_upload_dtype!r} (16-bit uploads)")
+        if self.device_upload_quant is not None:
+            raise refuse(f"device_upload_quant={self.device_upload_quant!r} (MXFP8 delta uploads)")
+        if self.device_upload_topk is not None:
+            raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -338,6 +368,9 @@ class DeviceAggregatorMixin:
             trim = self._trim_spec()
             if trim is not None:
                 kw["trim"] = trim
+            krum = self._krum_spec()
+            if krum is not None:
+                kw["krum"] = krum
             rnd = self._device_round = w.begin_round(self.tasks_round, self._device_policy(),
                                                      capacity=self.device_round_capacity,
                                                      keep_mean=self.device_keep_mean, **kw)
@@ -369,6 +402,10 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_trim is not None:
             from ...trim_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
+        if self.device_krum is not None:
+            from ...krum_round import refuse
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_upload_quant is not None:
@@ -424,6 +461,10 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         if self.device_trim is not None:
             from ...trim_round import refuse
+
+            raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
+        if self.device_krum is not None:
+            from ...krum_round import refuse
 
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         w = self.model_wrapper[cohort_id]

@@ -1,0 +1,11 @@
+#!/bin/bash
+# Time the Multi-Krum kernels beside fa_reduce at 100 x 1 M, 100 x 25 M and 1000 x 25 M (tools/krum_measure.py) and
+# leave profiles/krum_measure.{log,json}.  Run from the repository root on a machine with an MI355X, with
+# libfedagg.so already built (python -c "import __graft_entry__ as g; g.build()").  Every GPU step has its own time
+# limit and the steps are chained: a step that fails or hangs ends the script, nothing is started after it.
+set -o pipefail
+export OMP_NUM_THREADS=${OMP_NUM_THREADS:-16}
+mkdir -p profiles &&
+timeout -k 10 120 python -c "from fedscale_amd import _native_krum as nk; nk.load(); print('fedkrum ABI', nk.ABI_VERSION)" &&
+timeout -k 10 600 python -u tools/krum_measure.py --configs c2,k100,head --reps 20 --round-reps 5 \
+    --out profiles/krum_measure.json 2>&1 | tee profiles/krum_measure.log
