@@ -121,6 +121,12 @@ class DeviceAggregatorMixin:
     #: device_shards, device_upload_dtype, device_upload_quant, device_upload_topk, the async and the cohort mixin
     #: are refused with it
     device_krum = None
+    #: opt-in: the geometric median of the uploads (RFA) by the smoothed Weiszfeld iteration on the device — nothing
+    #: to tune, breakdown point 1/2 (fedscale_amd/geomed_round.py; INTEGRATION.md, "Geometric-median aggregation").
+    #: True (4 iterations, nu = 1e-6, method "auto"), an int (the iterations) or a GeoMedSpec.  FedAvg and fed-yogi;
+    #: q-FedAvg, device_clip_norm, device_trim, device_krum, device_shards, device_upload_dtype, device_upload_quant,
+    #: device_upload_topk, the async and the cohort mixin are refused with it
+    device_geomed = None
 
     _device_round = None
 
@@ -161,6 +167,31 @@ class DeviceAggregatorMixin:
             raise refuse("device_clip_norm (a norm-clipped round)")
         if self.device_trim is not None:
             raise refuse("device_trim (a trimmed-mean round)")
+        if self.device_upload_dtype is not None:
+            raise refuse(f"device_upload_dtype={self.device_upload_dtype!r} (16-bit uploads)")
+        if self.device_upload_quant is not None:
+            raise refuse(f"device_upload_quant={self.device_upload_quant!r} (MXFP8 delta uploads)")
+        if self.device_upload_topk is not None:
+            raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
+        if self.device_shards is not None and len(self.device_shards) > 1:
+            raise refuse("device_shards (a model sharded over several GPUs)")
+        return spec
+
+    def _geomed_spec(self):
+        """The ``GeoMedSpec`` of this aggregator's rounds (None: ``device_geomed`` is not set), after refusing the
+        attributes it does not combine with."""
+        g = self.device_geomed
+        if g is None:
+            return None
+        from ...geomed_round import GeoMedSpec, refuse
+
+        spec = GeoMedSpec.of(g)
+        if self.device_clip_norm is not None:
+            raise refuse("device_clip_norm (a norm-clipped round)")
+        if self.device_trim is not None:
+            raise refuse("device_trim (a trimmed-mean round)")
+        if self.device_krum is not None:
+            raise refuse("device_krum (a Multi-Krum round)")
         if self.device_upload_dtype is not None:
             raise refuse(f"device_upload_dtype={self.device_upload_dtype!r} (16-bit uploads)")
         if self.device_upload_quant is not None:
@@ -371,6 +402,9 @@ class DeviceAggregatorMixin:
             krum = self._krum_spec()
             if krum is not None:
                 kw["krum"] = krum
+            geomed = self._geomed_spec()
+            if geomed is not None:
+                kw["geomed"] = geomed
             rnd = self._device_round = w.begin_round(self.tasks_round, self._device_policy(),
                                                      capacity=self.device_round_capacity,
                                                      keep_mean=self.device_keep_mean, **kw)
@@ -406,6 +440,10 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_krum is not None:
             from ...krum_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
+        if self.device_geomed is not None:
+            from ...geomed_round import refuse
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_upload_quant is not None:
@@ -465,6 +503,10 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         if self.device_krum is not None:
             from ...krum_round import refuse
+
+            raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
+        if self.device_geomed is not None:
+            from ...geomed_round import refuse
 
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         w = self.model_wrapper[cohort_id]

@@ -243,7 +243,11 @@ class ShardedModelAdapter(TorchModelAdapter):
 
     # ---- rounds -----------------------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
-                    signatures: bool = False, clip=None, trim=None, krum=None) -> ShardedRound:
+                    signatures: bool = False, clip=None, trim=None, krum=None, geomed=None) -> ShardedRound:
+        if geomed is not None:  # geometric-median rounds (fedscale_amd/geomed_round.py): one whole model on one device
+            from ...geomed_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)")
         if krum is not None:  # Krum rounds (fedscale_amd/krum_round.py): one whole model on one device
             from ...krum_round import refuse
 
