@@ -127,8 +127,52 @@ class DeviceAggregatorMixin:
     #: q-FedAvg, device_clip_norm, device_trim, device_krum, device_shards, device_upload_dtype, device_upload_quant,
     #: device_upload_topk, the async and the cohort mixin are refused with it
     device_geomed = None
+    #: opt-in: secure aggregation — a ``secagg_round.SecAggSpec`` (or True for its defaults): the executors upload
+    #: their update against the weights they were sent for this round as fixed-point integers mod 2^32 under
+    #: pseudorandom masks (fedscale_amd/cloud/execution/secagg_upload.py); the rows are summed mod 2^32 and unmasked on
+    #: the device with the keys ``device_secagg_unmask`` returns (fedscale_amd/secagg_round.py; INTEGRATION.md, "Secure
+    #: aggregation").  FedAvg and fed-yogi; everything that needs individual uploads is refused with it: q-FedAvg,
+    #: device_clip_norm, device_trim, device_krum, device_geomed, device_shards, device_upload_dtype,
+    #: device_upload_quant, device_upload_topk, the async and the cohort mixin
+    device_upload_secagg = None
 
     _device_round = None
+
+    def device_secagg_unmask(self, client_ids):
+        """The hook of ``device_upload_secagg``, called once at round close with the arrived clients' ids in arrival
+        order: return ``(sub_keys, add_keys, nonce)`` for ``SecAggRound.unmask`` — the keys the deployment's protocol
+        reconstructed: the arrived clients' self-mask keys and, for every neighbour of theirs that dropped, the
+        pairwise key with the sign that cancels what the arrived client applied."""
+        raise NotImplementedError("device_upload_secagg is set but device_secagg_unmask(client_ids) -> (sub_keys, "
+                                  "add_keys, nonce) is not implemented: override the hook device_secagg_unmask to hand "
+                                  "the round the keys your secure-aggregation protocol reconstructed")
+
+    def _secagg_spec(self):
+        """The ``SecAggSpec`` of this aggregator's rounds (None: ``device_upload_secagg`` is not set), after refusing
+        the attributes it does not combine with."""
+        s = self.device_upload_secagg
+        if s is None:
+            return None
+        from ...secagg_round import SecAggSpec, refuse
+
+        spec = SecAggSpec.of(s)
+        if self.device_clip_norm is not None:
+            raise refuse("device_clip_norm (a norm-clipped round)")
+        if self.device_trim is not None:
+            raise refuse("device_trim (a trimmed-mean round)")
+        if self.device_krum is not None:
+            raise refuse("device_krum (a Multi-Krum round)")
+        if self.device_geomed is not None:
+            raise refuse("device_geomed (a geometric-median round)")
+        if self.device_upload_dtype is not None:
+            raise refuse(f"device_upload_dtype={self.device_upload_dtype!r} (16-bit uploads)")
+        if self.device_upload_quant is not None:
+            raise refuse(f"device_upload_quant={self.device_upload_quant!r} (MXFP8 delta uploads)")
+        if self.device_upload_topk is not None:
+            raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
+        if self.device_shards is not None and len(self.device_shards) > 1:
+            raise refuse("device_shards (a model sharded over several GPUs)")
+        return spec
 
     def _clip_spec(self):
         """The ``ClipSpec`` of this aggregator's rounds (None: ``device_clip_norm`` is not set)."""
@@ -248,6 +292,8 @@ class DeviceAggregatorMixin:
                 kw["upload_quant"] = self.device_upload_quant
             if self.device_upload_topk is not None:
                 kw["upload_topk"] = self.device_upload_topk
+            if self.device_upload_secagg is not None:
+                kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
         else:
             dev = devs[0] if devs else self._aggregation_device()
@@ -257,6 +303,8 @@ class DeviceAggregatorMixin:
                 kw["upload_quant"] = self.device_upload_quant
             if self.device_upload_topk is not None:
                 kw["upload_topk"] = self.device_upload_topk
+            if self.device_upload_secagg is not None:
+                kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
             if self.device_numa_bind:
                 from ...hostnuma import bind_to_gpu
@@ -394,6 +442,12 @@ class DeviceAggregatorMixin:
         rnd = self._device_round
         if rnd is None or self._is_first_result_in_round():
             w = self._wrapper()
+            secagg = self._secagg_spec()  # (refuses what it does not combine with, before a device is touched)
+            if secagg is not None:
+                if getattr(w, "upload_secagg", None) != secagg:
+                    raise ValueError(f"device_upload_secagg={secagg!r} but the model wrapper was built with "
+                                     f"upload_secagg={getattr(w, 'upload_secagg', None)!r}")
+            self._secagg_clients = []  # a masked round's client ids, in arrival order (device_secagg_unmask)
             clip = self._clip_spec()
             kw = {} if clip is None else {"clip": clip}  # (unset, the call is what it was)
             trim = self._trim_spec()
@@ -416,9 +470,15 @@ class DeviceAggregatorMixin:
                 results["update_weight"] = StagedUpload(rnd.n - 1)
         else:
             rnd.add(results["update_weight"])
+        masked = getattr(rnd, "upload_secagg", None) is not None
+        if masked:
+            self._secagg_clients.append(results.get("client_id"))  # arrival order
         if self._is_last_result_in_round():
             w = self._wrapper()
             K = self.tasks_round
+            if masked:
+                sub_keys, add_keys, nonce = self.device_secagg_unmask(list(self._secagg_clients))
+                rnd.unmask(sub_keys, add_keys, nonce)
             # np.divide(w, K): fp32 entries divide by fp32(K), int64 sums by float64(K)
             w.apply_round(rnd, float(np.float32(K)), float(K),
                           client_training_results=self.client_training_results, keep_mean=self.device_keep_mean)
@@ -456,6 +516,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_topk)
+        if self.device_upload_secagg is not None:
+            from ...secagg_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model, "
+                         "and staleness weights are per client)")
         w = self._wrapper()
         # async_aggregator.py:125-126 — Python-float weight and denominator
         s = 1 / (1 + self.round - self.client_task_model_version[results["client_id"]]) ** 0.5
@@ -509,6 +574,10 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
             from ...geomed_round import refuse
 
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
+        if self.device_upload_secagg is not None:
+            from ...secagg_round import refuse
+
+            raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds: clustering needs individual uploads)")
         w = self.model_wrapper[cohort_id]
         if not isinstance(w, TorchModelAdapter):
             raise TypeError(f"model_wrapper[{cohort_id}] is {type(w).__name__}; the device path needs "

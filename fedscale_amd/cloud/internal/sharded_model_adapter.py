@@ -82,7 +82,7 @@ class ShardedModelAdapter(TorchModelAdapter):
 
     def __init__(self, model: torch.nn.Module, optimizer=None, devices=None, staging_capacity: Optional[int] = None,
                  transport: Optional[str] = None, upload_dtype: Optional[str] = None,
-                 upload_quant: Optional[str] = None, upload_topk: Optional[float] = None):
+                 upload_quant: Optional[str] = None, upload_topk: Optional[float] = None, upload_secagg=None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
@@ -95,6 +95,10 @@ class ShardedModelAdapter(TorchModelAdapter):
             from ...sparse_round import refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_topk)
+        if upload_secagg is not None:  # secure-aggregation uploads (fedscale_amd/secagg_round.py): likewise
+            from ...secagg_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)")
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -149,6 +149,27 @@ def _rebuild_with_upload_topk(cls, model, optimizer, density):
     return cls(model, optimizer, upload_topk=density)
 
 
+def _takes_upload_secagg(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_secagg`` — wired as
+    ``_takes_upload_topk`` wires its option: set on the instance before the constructor's body runs (which refuses
+    what it does not combine with); an adapter that has it pickles through ``_rebuild_with_upload_secagg``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_secagg=None, **kw):
+        if upload_secagg is not None:
+            from ...secagg_round import SecAggSpec
+
+            self.upload_secagg = SecAggSpec.of(upload_secagg)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_secagg(cls, model, optimizer, spec):
+    """Unpickle an adapter with ``upload_secagg`` (``TorchModelAdapter.__reduce__``)."""
+    return cls(model, optimizer, upload_secagg=spec)
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -163,9 +184,13 @@ class TorchModelAdapter(ModelAdapterBase):
     upload_quant = None
     #: a density in (0, 1]: the clients upload top-k sparse deltas against the round's model (None: whole weights)
     upload_topk = None
+    #: a ``secagg_round.SecAggSpec``: the clients upload masked fixed-point updates against the round's model, summed
+    #: mod 2^32 and unmasked on the device (None: whole weights, in the clear)
+    upload_secagg = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_secagg
     @_takes_upload_topk
     def __init__(self, model: torch.nn.Module, optimizer=None, device=None, shards: Optional[ShardGroup] = None,
                  staging_capacity: Optional[int] = None, _load_from=None, dstream: Optional[DeviceStream] = None,
@@ -180,7 +205,11 @@ class TorchModelAdapter(ModelAdapterBase):
         weights): clients upload the largest-magnitude ``ceil(density * P)`` entries of their update against the
         weights they were sent for this round, as (index, value) pairs
         (fedscale_amd/cloud/execution/sparse_upload.py); ``begin_round`` then returns a ``SparseRound`` over a
-        ``SparseStaging`` (fedscale_amd/sparse_round.py)."""
+        ``SparseStaging`` (fedscale_amd/sparse_round.py).
+        ``upload_secagg`` (keyword only, taken by ``_takes_upload_secagg``; a ``secagg_round.SecAggSpec`` or True for
+        its defaults; None: uploads in the clear): clients upload their update against the weights they were sent for
+        this round as masked fixed-point integers mod 2^32 (fedscale_amd/cloud/execution/secagg_upload.py);
+        ``begin_round`` then returns a ``SecAggRound`` over a ``MaskedStaging`` (fedscale_amd/secagg_round.py)."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -217,6 +246,19 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse_s("a sharded model or client-sharded ranks (ShardGroup)", topk)
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse_s("the q-fedavg server optimizer", topk)
+        if self.__dict__.get("upload_secagg") is not None:  # set by _takes_upload_secagg before this body runs
+            from ...secagg_round import refuse as refuse_a
+
+            if self.upload_dtype is not None:
+                raise refuse_a(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)")
+            if self.upload_quant is not None:
+                raise refuse_a(f"upload_quant={self.upload_quant!r} (MXFP8 delta uploads)")
+            if topk is not None:
+                raise refuse_a(f"upload_topk={topk!r} (top-k sparse delta uploads)")
+            if shards is not None and shards.world != 1:
+                raise refuse_a("a sharded model or client-sharded ranks (ShardGroup)")
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse_a("the q-fedavg server optimizer")
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -532,6 +574,9 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if getattr(self, "upload_secagg", None) is not None:
+            return (_rebuild_with_upload_secagg, (self.__class__, self.get_model(), self.optimizer,
+                                                  self.upload_secagg))
         if getattr(self, "upload_topk", None) is not None:
             return (_rebuild_with_upload_topk, (self.__class__, self.get_model(), self.optimizer, self.upload_topk))
         if self.upload_quant is not None:
@@ -561,6 +606,8 @@ class TorchModelAdapter(ModelAdapterBase):
         ``geomed`` (a ``geomed_round.GeoMedSpec``, an int — its iterations — or True; FedAvg rounds): the new model is
         the geometric median of the uploads by the smoothed Weiszfeld iteration — a ``GeoMedRound``
         (fedscale_amd/geomed_round.py), which needs all K uploads resident."""
+        if getattr(self, "upload_secagg", None) is not None:
+            return self._begin_secagg_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
         if geomed is not None:
             geomed = self._check_geomed(policy, signatures, clip, trim, krum, geomed)
             geomed.resolve(K)  # (a K the round cannot take is refused here, with nothing allocated)
@@ -820,6 +867,42 @@ class TorchModelAdapter(ModelAdapterBase):
         return SparseRound(self.layout, self.device, K, policy, staging=self.staging, last_f32=self._snapshot().f32,
                            capacity=want, dstream=self.dstream)
 
+    def _begin_secagg_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
+                            geomed):
+        """``begin_round`` of an adapter with ``upload_secagg``: a ``SecAggRound`` over a ``MaskedStaging`` whose
+        default capacity is computed from rows of 4 bytes per parameter.  The combinations secure aggregation does
+        not take, and a K whose sum could wrap mod 2^32, are refused here, before a device is touched."""
+        from ...secagg_round import MaskedStaging, SecAggRound, default_capacity_secagg, refuse
+
+        spec = self.upload_secagg
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)")
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)")
+        if krum is not None:
+            raise refuse("krum (a Multi-Krum round)")
+        if geomed is not None:
+            raise refuse("geomed (a geometric-median round)")
+        if signatures:
+            raise refuse("cohort signatures")
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round")
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)")
+        spec.check_clients(K)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            want = default_capacity_secagg(self.layout, K, self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = MaskedStaging(self.layout, self.device, want, dstream=self.dstream)
+        return SecAggRound(self.layout, self.device, K, policy, spec, staging=self.staging,
+                           last_f32=self._snapshot().f32, capacity=want, dstream=self.dstream)
+
     def apply_round(self, rnd: DeviceRound, denom32: float, denom64: float, client_training_results=None,
                     keep_mean: bool = True):
         """Finish a round: reduce the last chunk with the server step fused, then swap buffers."""
@@ -908,6 +991,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "upload_quant", None) is not None:  # a QuantRound finishes through fcl_finish
             return False
         if getattr(rnd, "upload_topk", None) is not None:  # a SparseRound finishes through fcl_finish
+            return False
+        if getattr(rnd, "upload_secagg", None) is not None:  # a SecAggRound finishes through fsa_finish
             return False
         if getattr(rnd, "clip", None) is not None:  # a ClippedRound finishes through fcl_finish
             return False
