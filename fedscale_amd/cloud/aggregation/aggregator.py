@@ -99,6 +99,13 @@ class DeviceAggregatorMixin:
     #: FedAvg and fed-yogi; q-FedAvg, device_shards, device_upload_dtype, device_upload_quant, device_clip_norm,
     #: device_trim, the async and the cohort mixin's signatures are refused with it
     device_upload_topk = None
+    #: opt-in: "sign1" — the executors upload the scaled sign of their update against the weights they were sent for
+    #: this round, one bit per parameter and one float32 scale per block of 256
+    #: (fedscale_amd/cloud/execution/sign_upload.py: lossy on the wire, exact from there on; error feedback is the
+    #: executor's state); staged in HBM at 9/64 byte per parameter and chained in fp32 (fedscale_amd/sign_round.py).
+    #: FedAvg and fed-yogi; q-FedAvg, device_shards, the other upload formats, device_clip_norm, device_trim,
+    #: device_krum, device_geomed, device_upload_secagg, the async and the cohort mixin's signatures are refused with it
+    device_upload_sign = None
     #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
     #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
     #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
@@ -170,6 +177,8 @@ class DeviceAggregatorMixin:
             raise refuse(f"device_upload_quant={self.device_upload_quant!r} (MXFP8 delta uploads)")
         if self.device_upload_topk is not None:
             raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
+        if self.device_upload_sign is not None:
+            raise refuse(f"device_upload_sign={self.device_upload_sign!r} (1-bit sign delta uploads)")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -217,6 +226,8 @@ class DeviceAggregatorMixin:
             raise refuse(f"device_upload_quant={self.device_upload_quant!r} (MXFP8 delta uploads)")
         if self.device_upload_topk is not None:
             raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
+        if self.device_upload_sign is not None:
+            raise refuse(f"device_upload_sign={self.device_upload_sign!r} (1-bit sign delta uploads)")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -242,6 +253,8 @@ class DeviceAggregatorMixin:
             raise refuse(f"device_upload_quant={self.device_upload_quant!r} (MXFP8 delta uploads)")
         if self.device_upload_topk is not None:
             raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
+        if self.device_upload_sign is not None:
+            raise refuse(f"device_upload_sign={self.device_upload_sign!r} (1-bit sign delta uploads)")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -292,6 +305,8 @@ class DeviceAggregatorMixin:
                 kw["upload_quant"] = self.device_upload_quant
             if self.device_upload_topk is not None:
                 kw["upload_topk"] = self.device_upload_topk
+            if self.device_upload_sign is not None:
+                kw["upload_sign"] = self.device_upload_sign
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
@@ -303,6 +318,8 @@ class DeviceAggregatorMixin:
                 kw["upload_quant"] = self.device_upload_quant
             if self.device_upload_topk is not None:
                 kw["upload_topk"] = self.device_upload_topk
+            if self.device_upload_sign is not None:
+                kw["upload_sign"] = self.device_upload_sign
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
@@ -516,6 +533,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_topk)
+        if self.device_upload_sign is not None:
+            from ...sign_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
+                         self.device_upload_sign)
         if self.device_upload_secagg is not None:
             from ...secagg_round import refuse
 

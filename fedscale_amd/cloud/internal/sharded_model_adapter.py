@@ -82,7 +82,8 @@ class ShardedModelAdapter(TorchModelAdapter):
 
     def __init__(self, model: torch.nn.Module, optimizer=None, devices=None, staging_capacity: Optional[int] = None,
                  transport: Optional[str] = None, upload_dtype: Optional[str] = None,
-                 upload_quant: Optional[str] = None, upload_topk: Optional[float] = None, upload_secagg=None):
+                 upload_quant: Optional[str] = None, upload_topk: Optional[float] = None, upload_secagg=None,
+                 upload_sign: Optional[str] = None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
@@ -99,6 +100,10 @@ class ShardedModelAdapter(TorchModelAdapter):
             from ...secagg_round import refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)")
+        if upload_sign is not None:  # 1-bit sign delta uploads (fedscale_amd/sign_round.py): likewise
+            from ...sign_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_sign)
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -170,6 +170,27 @@ def _rebuild_with_upload_secagg(cls, model, optimizer, spec):
     return cls(model, optimizer, upload_secagg=spec)
 
 
+def _takes_upload_sign(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_sign`` — wired as
+    ``_takes_upload_topk`` wires its option: set on the instance before the constructor's body runs (which refuses
+    what it does not combine with); an adapter that has it pickles through ``_rebuild_with_upload_sign``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_sign: Optional[str] = None, **kw):
+        if upload_sign is not None:
+            from ...sign_round import check_format
+
+            self.upload_sign = check_format(upload_sign)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_sign(cls, model, optimizer, fmt):
+    """Unpickle an adapter with ``upload_sign`` (``TorchModelAdapter.__reduce__``)."""
+    return cls(model, optimizer, upload_sign=fmt)
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -187,9 +208,13 @@ class TorchModelAdapter(ModelAdapterBase):
     #: a ``secagg_round.SecAggSpec``: the clients upload masked fixed-point updates against the round's model, summed
     #: mod 2^32 and unmasked on the device (None: whole weights, in the clear)
     upload_secagg = None
+    #: "sign1": the clients upload the scaled sign of their update against the round's model, one bit per parameter
+    #: and one float32 scale per block of 256 (None: whole weights)
+    upload_sign = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_sign
     @_takes_upload_secagg
     @_takes_upload_topk
     def __init__(self, model: torch.nn.Module, optimizer=None, device=None, shards: Optional[ShardGroup] = None,
@@ -209,7 +234,11 @@ class TorchModelAdapter(ModelAdapterBase):
         ``upload_secagg`` (keyword only, taken by ``_takes_upload_secagg``; a ``secagg_round.SecAggSpec`` or True for
         its defaults; None: uploads in the clear): clients upload their update against the weights they were sent for
         this round as masked fixed-point integers mod 2^32 (fedscale_amd/cloud/execution/secagg_upload.py);
-        ``begin_round`` then returns a ``SecAggRound`` over a ``MaskedStaging`` (fedscale_amd/secagg_round.py)."""
+        ``begin_round`` then returns a ``SecAggRound`` over a ``MaskedStaging`` (fedscale_amd/secagg_round.py).
+        ``upload_sign`` (keyword only, taken by ``_takes_upload_sign``; "sign1"; None: whole weights): clients upload
+        the scaled sign of their update against the weights they were sent for this round, one bit per parameter and
+        one float32 scale per block of 256 (fedscale_amd/cloud/execution/sign_upload.py); ``begin_round`` then returns
+        a ``SignRound`` over a ``SignStaging`` (fedscale_amd/sign_round.py)."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -259,6 +288,22 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse_a("a sharded model or client-sharded ranks (ShardGroup)")
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse_a("the q-fedavg server optimizer")
+        sign = self.__dict__.get("upload_sign")  # set by _takes_upload_sign before this body runs
+        if sign is not None:
+            from ...sign_round import refuse as refuse_g
+
+            if self.upload_dtype is not None:
+                raise refuse_g(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)", sign)
+            if self.upload_quant is not None:
+                raise refuse_g(f"upload_quant={self.upload_quant!r} (MXFP8 delta uploads)", sign)
+            if topk is not None:
+                raise refuse_g(f"upload_topk={topk!r} (top-k sparse delta uploads)", sign)
+            if self.__dict__.get("upload_secagg") is not None:
+                raise refuse_g("upload_secagg (secure-aggregation uploads)", sign)
+            if shards is not None and shards.world != 1:
+                raise refuse_g("a sharded model or client-sharded ranks (ShardGroup)", sign)
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse_g("the q-fedavg server optimizer", sign)
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -577,6 +622,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(self, "upload_secagg", None) is not None:
             return (_rebuild_with_upload_secagg, (self.__class__, self.get_model(), self.optimizer,
                                                   self.upload_secagg))
+        if getattr(self, "upload_sign", None) is not None:
+            return (_rebuild_with_upload_sign, (self.__class__, self.get_model(), self.optimizer, self.upload_sign))
         if getattr(self, "upload_topk", None) is not None:
             return (_rebuild_with_upload_topk, (self.__class__, self.get_model(), self.optimizer, self.upload_topk))
         if self.upload_quant is not None:
@@ -614,6 +661,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if krum is not None:
             krum = self._check_krum(policy, signatures, clip, trim, krum)
             krum.counts(K)  # (counts the round cannot take are refused here, with nothing allocated)
+        if getattr(self, "upload_sign", None) is not None:
+            return self._begin_sign_round(K, policy, capacity, signatures, clip, trim)
         if getattr(self, "upload_topk", None) is not None:
             return self._begin_sparse_round(K, policy, capacity, signatures, clip, trim)
         if getattr(self, "upload_quant", None) is not None:
@@ -735,6 +784,8 @@ class TorchModelAdapter(ModelAdapterBase):
             raise refuse("clip (a norm-clipped round)")
         if trim is not None:
             raise refuse("trim (a trimmed-mean round)")
+        if getattr(self, "upload_sign", None) is not None:
+            raise refuse(f"upload_sign={self.upload_sign!r} (1-bit sign delta uploads)")
         if getattr(self, "upload_topk", None) is not None:
             raise refuse(f"upload_topk={self.upload_topk!r} (top-k sparse delta uploads)")
         if getattr(self, "upload_quant", None) is not None:
@@ -765,6 +816,8 @@ class TorchModelAdapter(ModelAdapterBase):
             raise refuse("trim (a trimmed-mean round)")
         if krum is not None:
             raise refuse("krum (a Multi-Krum round)")
+        if getattr(self, "upload_sign", None) is not None:
+            raise refuse(f"upload_sign={self.upload_sign!r} (1-bit sign delta uploads)")
         if getattr(self, "upload_topk", None) is not None:
             raise refuse(f"upload_topk={self.upload_topk!r} (top-k sparse delta uploads)")
         if getattr(self, "upload_quant", None) is not None:
@@ -867,6 +920,36 @@ class TorchModelAdapter(ModelAdapterBase):
         return SparseRound(self.layout, self.device, K, policy, staging=self.staging, last_f32=self._snapshot().f32,
                            capacity=want, dstream=self.dstream)
 
+    def _begin_sign_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim):
+        """``begin_round`` of an adapter with ``upload_sign``: a ``SignRound`` over a ``SignStaging`` whose default
+        capacity is computed from rows of 9/64 byte per parameter.  The combinations the sign-delta path does not take
+        are refused here, before a device is touched."""
+        from ...sign_round import SignRound, SignStaging, default_capacity_sign, refuse
+
+        fmt = self.upload_sign
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)", fmt)
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)", fmt)
+        if signatures:
+            raise refuse("cohort signatures", fmt)
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round", fmt)
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)", fmt)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            want = default_capacity_sign(self.layout, K, self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = SignStaging(self.layout, self.device, want, dstream=self.dstream)
+        return SignRound(self.layout, self.device, K, policy, staging=self.staging, last_f32=self._snapshot().f32,
+                         capacity=want, dstream=self.dstream)
+
     def _begin_secagg_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
                             geomed):
         """``begin_round`` of an adapter with ``upload_secagg``: a ``SecAggRound`` over a ``MaskedStaging`` whose
@@ -875,6 +958,8 @@ class TorchModelAdapter(ModelAdapterBase):
         from ...secagg_round import MaskedStaging, SecAggRound, default_capacity_secagg, refuse
 
         spec = self.upload_secagg
+        if getattr(self, "upload_sign", None) is not None:
+            raise refuse(f"upload_sign={self.upload_sign!r} (1-bit sign delta uploads)")
         if clip is not None:
             raise refuse("clip (a norm-clipped round)")
         if trim is not None:
@@ -991,6 +1076,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "upload_quant", None) is not None:  # a QuantRound finishes through fcl_finish
             return False
         if getattr(rnd, "upload_topk", None) is not None:  # a SparseRound finishes through fcl_finish
+            return False
+        if getattr(rnd, "upload_sign", None) is not None:  # a SignRound finishes through fcl_finish
             return False
         if getattr(rnd, "upload_secagg", None) is not None:  # a SecAggRound finishes through fsa_finish
             return False
