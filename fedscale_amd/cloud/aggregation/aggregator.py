@@ -106,6 +106,11 @@ class DeviceAggregatorMixin:
     #: FedAvg and fed-yogi; q-FedAvg, device_shards, the other upload formats, device_clip_norm, device_trim,
     #: device_krum, device_geomed, device_upload_secagg, the async and the cohort mixin's signatures are refused with it
     device_upload_sign = None
+    #: opt-in, with device_upload_sign: "rht4096" — the executors rotate their update by a seeded 4096-point block
+    #: Hadamard transform before the sign encoder sees it (fedscale_amd/cloud/execution/rotate_upload.py), which makes
+    #: the 1-bit encoding's fidelity independent of the update's distribution; the round rotates its chain back once
+    #: (fedscale_amd/rotate_round.py).  Refused wherever device_upload_sign is, and without it
+    device_upload_rotate = None
     #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
     #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
     #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
@@ -179,6 +184,8 @@ class DeviceAggregatorMixin:
             raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
         if self.device_upload_sign is not None:
             raise refuse(f"device_upload_sign={self.device_upload_sign!r} (1-bit sign delta uploads)")
+        if self.device_upload_rotate is not None:
+            raise refuse(f"device_upload_rotate={self.device_upload_rotate!r} (rotated 1-bit sign delta uploads)")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -228,6 +235,8 @@ class DeviceAggregatorMixin:
             raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
         if self.device_upload_sign is not None:
             raise refuse(f"device_upload_sign={self.device_upload_sign!r} (1-bit sign delta uploads)")
+        if self.device_upload_rotate is not None:
+            raise refuse(f"device_upload_rotate={self.device_upload_rotate!r} (rotated 1-bit sign delta uploads)")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -255,6 +264,8 @@ class DeviceAggregatorMixin:
             raise refuse(f"device_upload_topk={self.device_upload_topk!r} (top-k sparse delta uploads)")
         if self.device_upload_sign is not None:
             raise refuse(f"device_upload_sign={self.device_upload_sign!r} (1-bit sign delta uploads)")
+        if self.device_upload_rotate is not None:
+            raise refuse(f"device_upload_rotate={self.device_upload_rotate!r} (rotated 1-bit sign delta uploads)")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -307,6 +318,8 @@ class DeviceAggregatorMixin:
                 kw["upload_topk"] = self.device_upload_topk
             if self.device_upload_sign is not None:
                 kw["upload_sign"] = self.device_upload_sign
+            if self.device_upload_rotate is not None:
+                kw["upload_rotate"] = self.device_upload_rotate
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
@@ -320,6 +333,8 @@ class DeviceAggregatorMixin:
                 kw["upload_topk"] = self.device_upload_topk
             if self.device_upload_sign is not None:
                 kw["upload_sign"] = self.device_upload_sign
+            if self.device_upload_rotate is not None:
+                kw["upload_rotate"] = self.device_upload_rotate
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
@@ -538,6 +553,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_sign)
+        if self.device_upload_rotate is not None:
+            from ...rotate_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
+                         self.device_upload_rotate)
         if self.device_upload_secagg is not None:
             from ...secagg_round import refuse
 

@@ -83,7 +83,7 @@ class ShardedModelAdapter(TorchModelAdapter):
     def __init__(self, model: torch.nn.Module, optimizer=None, devices=None, staging_capacity: Optional[int] = None,
                  transport: Optional[str] = None, upload_dtype: Optional[str] = None,
                  upload_quant: Optional[str] = None, upload_topk: Optional[float] = None, upload_secagg=None,
-                 upload_sign: Optional[str] = None):
+                 upload_sign: Optional[str] = None, upload_rotate: Optional[str] = None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
@@ -104,6 +104,10 @@ class ShardedModelAdapter(TorchModelAdapter):
             from ...sign_round import refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_sign)
+        if upload_rotate is not None:  # rotated sign uploads (fedscale_amd/rotate_round.py): likewise
+            from ...rotate_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_rotate)
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -191,6 +191,27 @@ def _rebuild_with_upload_sign(cls, model, optimizer, fmt):
     return cls(model, optimizer, upload_sign=fmt)
 
 
+def _takes_upload_rotate(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_rotate`` — wired as
+    ``_takes_upload_topk`` wires its option: set on the instance before the constructor's body runs (which refuses it
+    without ``upload_sign``); an adapter that has it pickles through ``_rebuild_with_upload_rotate``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_rotate: Optional[str] = None, **kw):
+        if upload_rotate is not None:
+            from ...rotate_round import check_rotation
+
+            self.upload_rotate = check_rotation(upload_rotate)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_rotate(cls, model, optimizer, fmt, rot):
+    """Unpickle an adapter with ``upload_rotate`` (``TorchModelAdapter.__reduce__``)."""
+    return cls(model, optimizer, upload_sign=fmt, upload_rotate=rot)
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -211,9 +232,13 @@ class TorchModelAdapter(ModelAdapterBase):
     #: "sign1": the clients upload the scaled sign of their update against the round's model, one bit per parameter
     #: and one float32 scale per block of 256 (None: whole weights)
     upload_sign = None
+    #: "rht4096" (with ``upload_sign``): the clients rotate their update by a seeded 4096-point block Hadamard
+    #: transform before the sign encoder sees it, and the round rotates its chain back once (None: no rotation)
+    upload_rotate = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_rotate
     @_takes_upload_sign
     @_takes_upload_secagg
     @_takes_upload_topk
@@ -238,7 +263,11 @@ class TorchModelAdapter(ModelAdapterBase):
         ``upload_sign`` (keyword only, taken by ``_takes_upload_sign``; "sign1"; None: whole weights): clients upload
         the scaled sign of their update against the weights they were sent for this round, one bit per parameter and
         one float32 scale per block of 256 (fedscale_amd/cloud/execution/sign_upload.py); ``begin_round`` then returns
-        a ``SignRound`` over a ``SignStaging`` (fedscale_amd/sign_round.py)."""
+        a ``SignRound`` over a ``SignStaging`` (fedscale_amd/sign_round.py).
+        ``upload_rotate`` (keyword only, taken by ``_takes_upload_rotate``; "rht4096"; needs ``upload_sign``): clients
+        rotate their update by the seeded block Hadamard transform of include/fedrotate.h before it is encoded
+        (fedscale_amd/cloud/execution/rotate_upload.py); ``begin_round`` then returns a ``RotatedSignRound`` over a
+        ``RotatedSignStaging`` (fedscale_amd/rotate_round.py)."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -304,6 +333,11 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse_g("a sharded model or client-sharded ranks (ShardGroup)", sign)
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse_g("the q-fedavg server optimizer", sign)
+        rot = self.__dict__.get("upload_rotate")  # set by _takes_upload_rotate before this body runs
+        if rot is not None and sign is None:
+            from ...rotate_round import refuse as refuse_r
+
+            raise refuse_r("no upload_sign (the rotation goes around the 1-bit sign encoder)", rot)
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -622,6 +656,9 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(self, "upload_secagg", None) is not None:
             return (_rebuild_with_upload_secagg, (self.__class__, self.get_model(), self.optimizer,
                                                   self.upload_secagg))
+        if getattr(self, "upload_rotate", None) is not None:
+            return (_rebuild_with_upload_rotate, (self.__class__, self.get_model(), self.optimizer, self.upload_sign,
+                                                  self.upload_rotate))
         if getattr(self, "upload_sign", None) is not None:
             return (_rebuild_with_upload_sign, (self.__class__, self.get_model(), self.optimizer, self.upload_sign))
         if getattr(self, "upload_topk", None) is not None:
@@ -926,6 +963,9 @@ class TorchModelAdapter(ModelAdapterBase):
         are refused here, before a device is touched."""
         from ...sign_round import SignRound, SignStaging, default_capacity_sign, refuse
 
+        if getattr(self, "upload_rotate", None) is not None:  # the same round over rows of P' rotated columns
+            from ...rotate_round import RotatedSignRound as SignRound  # noqa: F811
+            from ...rotate_round import RotatedSignStaging as SignStaging  # noqa: F811
         fmt = self.upload_sign
         if clip is not None:
             raise refuse("clip (a norm-clipped round)", fmt)
