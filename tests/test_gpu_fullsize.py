@@ -331,11 +331,12 @@ def test_c2_through_the_drop_in_from_host_updates(gpu_device):
 
 
 @pytest.mark.parametrize("K,P,weighted", [
-    (200, 1_000_003, False),    # one round, sw 5 (V = 8 variant), K x sw at the threshold
-    (200, 2_300_001, True),     # one round, sw 11 (V = 16), FedBuff weights
-    (1000, 3_125_056, False),   # the north star's per-GPU bucket at 8 GPUs (config 4's 25M / 8), sw 14
-    (100, 5_000_001, False),    # one round, sw 22 (V = 32)
-    (60, 9_000_001, True),      # two rounds of the capped grid at sw 23 (LOOP kernel, run-time width)
+    # the forms at 256 CUs (tests/reduce_fixtures.plan; tests/test_reduce_plan.py asserts them):
+    (200, 1_000_003, False),    # one round, (8,4) at sw 5, K x sw at the threshold
+    (200, 2_300_001, True),     # one round, (16,2) at sw 12, FedBuff weights
+    (1000, 3_125_056, False),   # the north star's per-GPU bucket at 8 GPUs (config 4's 25M / 8): (16,2) FULL, sw 16
+    (100, 5_000_001, False),    # one round over every CU (K < 200), (32,1) at sw 20
+    (60, 9_000_001, True),      # two column windows, one launch each, (32,1) at sw 23
 ])
 def test_reduce_balanced_plans_bit_exact(gpu_device, K, P, weighted):
     """The balanced launch plans of fa_reduce (run-time tile width, fedagg.hip launch_plan): every column
@@ -344,6 +345,7 @@ def test_reduce_balanced_plans_bit_exact(gpu_device, K, P, weighted):
     from fedscale_amd import kernels as kx
     from fedscale_amd import synth
     from fedscale_amd.bucket import round_up
+    from tests import reduce_fixtures
 
     seed = 300 + K
     ld = round_up(P, 64)
@@ -354,19 +356,12 @@ def test_reduce_balanced_plans_bit_exact(gpu_device, K, P, weighted):
     out = torch.empty(ld, device="cuda")
     denom = float(f(w.sum())) if weighted else float(f(K))
     kx.reduce(x, K, P, out, a=torch.from_numpy(w).cuda() if weighted else None, denom=denom, finalize=True)
-    # tile boundaries of the plan (4 waves x sw strips of 64 float4 per tile)
+    # tile boundaries of the plan, window seams included (4 waves x sw strips of 64 float4 per tile)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    S = (ld // 4 + 63) // 64
-    gb = cus * 224 // 256
-    sw1 = -(-S // (4 * gb))
-    if sw1 > 32:
-        cap = cus * 75 // 100
-        R = -(-S // (4 * 32 * cap))
-        sw = -(-S // (4 * R * cap))
-    else:
-        sw = sw1
-    span = 4 * sw * 64 * 4  # floats per tile
-    bounds = np.arange(span, P, span)
+    launches = reduce_fixtures.plan(cus, K, P, weighted)
+    assert len(launches) == kx.reduce_launches(K, P, weighted)
+    bounds = np.concatenate([4 * np.arange(L["col0"], L["end4"], 4 * L["sw"] * 64) for L in launches])
+    bounds = bounds[bounds > 0]
     cols = np.unique(np.concatenate([_sample_cols(P, n=2048, seed=K),
                                      np.clip(np.concatenate([bounds - 1, bounds]), 0, P - 1)]))
     acc = None
@@ -383,8 +378,9 @@ def test_reduce_balanced_plans_bit_exact(gpu_device, K, P, weighted):
 
 @pytest.mark.parametrize("K,P", [(200, 2_300_001), (150, 5_000_001), (1000, 3_125_056)])
 def test_reduce_yogi_balanced_plans_bit_exact(gpu_device, K, P):
-    """The fused FedYoGi epilogue on the balanced plans' run-time-width tiles (V = 16 and V = 32 variants
-    with sw < V): mean, m, v and the new model bit-exact to the IEEE numpy restatement, two rounds."""
+    """The fused FedYoGi epilogue on the balanced plans' tiles (at 256 CUs (16,2) at sw 12, (32,1) at sw 20 and
+    the FULL (16,2) form, sw 16): mean, m, v and the new model bit-exact to the IEEE numpy restatement, two
+    rounds."""
     from fedscale_amd import kernels as kx
     from fedscale_amd import synth
     from fedscale_amd.bucket import round_up
