@@ -26,12 +26,13 @@ SRCS = ("fedscale_amd/csrc/fedagg.hip", "fedscale_amd/csrc/client_update.hip", "
         "fedscale_amd/csrc/reduce_half.hip", "fedscale_amd/csrc/clip_reduce.hip", "fedscale_amd/csrc/trim_reduce.hip",
         "fedscale_amd/csrc/quant_reduce.hip", "fedscale_amd/csrc/sparse_reduce.hip", "fedscale_amd/csrc/krum_gram.hip",
         "fedscale_amd/csrc/geomed.hip", "fedscale_amd/csrc/secagg.hip", "fedscale_amd/csrc/sign_reduce.hip",
-        "fedscale_amd/csrc/rotate.hip")
+        "fedscale_amd/csrc/rotate.hip", "fedscale_amd/csrc/server_opt.hip")
 #: headers they include (every #include "..." of the library)
 HDRS = ("fedscale_amd/csrc/fa_device.h", "fedscale_amd/csrc/fa_common.h", "include/fedagg.h", "include/fedclient.h",
         "include/fedcohort.h", "include/fedhalf.h", "include/fedclip.h", "include/fedtrim.h", "include/fedquant.h",
         "include/fedsparse.h", "include/fedkrum.h", "include/fedgeomed.h",
-        "include/fedsecagg.h", "include/fedsign.h", "include/fedrotate.h")
+        "include/fedsecagg.h", "include/fedsign.h", "include/fedrotate.h",
+        "include/fedserveropt.h")
 FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall")
 LIB = os.path.join(ROOT, "fedscale_amd", "libfedagg.so")
 MARKER = b"FA_BUILD_ID="

@@ -19,7 +19,7 @@ it contributes nothing, but still counts in the denominator K (DP-FedAvg's fixed
 ``ClippedRound`` is what ``TorchModelAdapter._apply_round`` and the aggregator mixins use of ``DeviceRound``, over the
 ordinary fp32 ``ClientStaging``.  Opt-in (``TorchModelAdapter.begin_round(clip=ClipSpec(...))``,
 ``DeviceAggregatorMixin.device_clip_norm``); FedAvg and — as the clipped mean followed by the existing YoGi step —
-fed-yogi.  16-bit uploads, cohort signatures, sharded layouts, FedBuff and q-FedAvg are refused.
+fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  16-bit uploads, cohort signatures, sharded layouts, FedBuff and q-FedAvg are refused.
 """
 from __future__ import annotations
 

@@ -13,6 +13,11 @@ Accepted inputs:
 
 Modes (optimizers.py:43-108): ``"fed-yogi"`` -> YoGi step; ``"q-fedavg"`` -> q-FedAvg; anything else
 (None, "fed-avg", "fed-prox") -> no-op (FedAvg was applied by the aggregator).
+
+Beyond the reference: ``"fed-adam"``, ``"fed-adagrad"`` (Reddi et al. 2021, Algorithm 2) and ``"fed-avgm"`` (Hsu et
+al. 2019) -> the adaptive server step of fedscale_amd/utils/optimizer/adaptive.py.  Their hyper-parameters are read
+from ``args`` by ``getattr``: ``server_eta`` (1e-2; 1.0 for fed-avgm), ``server_tau`` (1e-3), ``server_beta`` (0.9),
+``server_beta2`` (0.99), ``server_v0`` (None: tau*tau).
 """
 from __future__ import annotations
 
@@ -22,6 +27,10 @@ from ... import kernels as kx
 from ...bucket import BucketLayout
 from ...round import DeviceRound
 from ...state import FlatState
+from ...utils.optimizer.adaptive import MODES as ADAPTIVE_MODES
+
+#: the modes whose update_round_gradient steps the model (every other mode returns: FedAvg was already applied)
+STEP_MODES = ("fed-yogi", "q-fedavg") + tuple(ADAPTIVE_MODES)
 
 
 class TorchServerOptimizer(object):
@@ -34,11 +43,17 @@ class TorchServerOptimizer(object):
 
             self.gradient_controller = YoGi(eta=args.yogi_eta, tau=args.yogi_tau, beta=args.yogi_beta,
                                             beta2=args.yogi_beta2)
+        elif mode in ADAPTIVE_MODES:
+            cls = ADAPTIVE_MODES[mode]
+            self.gradient_controller = cls(
+                eta=getattr(args, "server_eta", cls.DEFAULT_ETA), tau=getattr(args, "server_tau", 1e-3),
+                beta=getattr(args, "server_beta", 0.9), beta2=getattr(args, "server_beta2", 0.99),
+                v0=getattr(args, "server_v0", None))
 
     def for_shard(self, device) -> "TorchServerOptimizer":
         """The optimizer of one shard of a model sharded over the GPUs of this process: same mode and the
-        same live ``args`` (optimizers.py:69 reads the learning rate at step time), its own YoGi state
-        (m_t / v_t of the shard's parameters, yogi.py:11-19)."""
+        same live ``args`` (optimizers.py:69 reads the learning rate at step time), its own YoGi (or adaptive
+        optimizer) state (m_t / v_t of the shard's parameters, yogi.py:11-19)."""
         return TorchServerOptimizer(self.mode, self.args, device)
 
     # ---------------------------------------------------------------------------------------------
@@ -50,7 +65,7 @@ class TorchServerOptimizer(object):
         return torch.device(d)
 
     def update_round_gradient(self, last_model, current_model, target_model, client_training_results=None):
-        if self.mode not in ("fed-yogi", "q-fedavg"):
+        if self.mode not in STEP_MODES:
             return  # optimizers.py:106-108
         if isinstance(last_model, FlatState):
             return self._device_step(last_model, current_model, target_model, client_training_results)
@@ -71,6 +86,12 @@ class TorchServerOptimizer(object):
                          **y.fp32_hparams())
             y.step_side(current.side, last.side, model=out_s)
             y.initialized = True
+        elif self.mode in ADAPTIVE_MODES:
+            o = self.gradient_controller
+            o.bind(lay, last.f32.device)
+            o.step(current.f32, last.f32, out_f, lay.P)
+            # the int64 entries take the mean, as set_weights without a server step loads them (float32 -> int64)
+            out_s.copy_(current.side.to(torch.float32).to(torch.int64))
         else:
             rnd = results
             if not isinstance(rnd, DeviceRound):

@@ -36,7 +36,7 @@ import torch
 from ...bucket import BucketLayout, HostRow, PieceSegments, RegisteredUpload, default_pack_workers
 from ...round import default_capacity
 from ...state import DeviceGroup, PartOf, ShardGroup
-from .torch_model_adapter import TorchModelAdapter
+from .torch_model_adapter import _ADAPTIVE_MODES, TorchModelAdapter
 
 
 class ShardedRound:
@@ -300,8 +300,8 @@ class ShardedModelAdapter(TorchModelAdapter):
         self._commit()
         self._release_registrations(block=False)
 
-    #: FedAvg rounds (without a server step, or with FedYoGi's) finish every part with ONE native call per pass
-    #: (fa_reduce_parts, then fa_yogi_step_parts)
+    #: FedAvg rounds (without a server step, with FedYoGi's, or with FedAdam's / FedAdagrad's / FedAvgM's) finish every
+    #: part with ONE native call per pass (fa_reduce_parts, then fa_yogi_step_parts or fso_step_parts)
     FINISH_PARTS_AT_ONCE = True
 
     def _finish_parts_at_once(self, rnd: ShardedRound, denom32: float, denom64: float) -> bool:
@@ -317,11 +317,14 @@ class ShardedModelAdapter(TorchModelAdapter):
         opt = self.optimizer
         mode = getattr(opt, "mode", None) if opt is not None else None
         if (not self.FINISH_PARTS_AT_ONCE or rnd.policy != "fedavg" or len(self.parts) < 2
-                or mode not in (None, "fed-yogi") or any(r.cg is not None for r in rnd.rounds)):
+                or mode not in (None, "fed-yogi") + tuple(_ADAPTIVE_MODES)
+                or any(r.cg is not None for r in rnd.rounds)):
             return False
         yogi = mode == "fed-yogi"
-        ys = [p.optimizer.gradient_controller for p in self.parts] if yogi else None
-        if yogi and len({y.initialized for y in ys}) != 1:
+        adaptive = mode in _ADAPTIVE_MODES  # FedAdam / FedAdagrad / FedAvgM: fso_step_parts, state per part
+        stepped = yogi or adaptive
+        ys = [p.optimizer.gradient_controller for p in self.parts] if stepped else None
+        if stepped and len({y.initialized for y in ys}) != 1:
             return False
         xs, Ks, Ps, means, accs, lasts, outs = [], [], [], [], [], [], []
         for i, (p, r) in enumerate(zip(self.parts, rnd.rounds)):
@@ -329,7 +332,7 @@ class ShardedModelAdapter(TorchModelAdapter):
             r.staging.drain()
             out_f, out_s = p._scratch_buffers()
             mean_f = out_f
-            if yogi:
+            if stepped:
                 last = p._snapshot()
                 if ys[i].layout is None or p._mean_f is None or p._mean_f is last.f32 or p._mean_f is out_f:
                     with p.dstream:  # first round: the YoGi state and the mean buffer on the part's device
@@ -350,6 +353,13 @@ class ShardedModelAdapter(TorchModelAdapter):
             y0 = ys[0]
             kx.yogi_step_parts(means, [last.f32 for last in lasts], [y.m for y in ys], [y.v for y in ys],
                                [o[0] for o in outs], Ps, streams, init=not y0.initialized, **y0.fp32_hparams())
+        elif adaptive:
+            from ... import kernels_serveropt as kso
+
+            y0 = ys[0]
+            kso.step_parts(y0.rule, means, [last.f32 for last in lasts], [y.m for y in ys],
+                           [y.v for y in ys] if y0.has_v else None, [o[0] for o in outs], Ps, streams,
+                           **y0.step_args())
         for i, (p, r) in enumerate(zip(self.parts, rnd.rounds)):
             out_f, out_s = outs[i]
             with p.dstream.joined():  # the caller's stream on this GPU is ordered after the part's work
@@ -360,6 +370,8 @@ class ShardedModelAdapter(TorchModelAdapter):
                               model=None if yogi else out_s)
                 if yogi:
                     ys[i].step_side(p._mean_s, lasts[i].side, model=out_s)
+                    ys[i].initialized = True
+                elif adaptive:  # the int64 entries took the mean above: they have no optimizer state
                     ys[i].initialized = True
                 else:
                     p._mean_f = out_f

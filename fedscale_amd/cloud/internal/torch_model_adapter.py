@@ -32,7 +32,11 @@ from ..._native import FA_ACCUMULATE, FA_FINALIZE
 from ...kernels import qfed_max_chunk as kx_qfed_max_chunk
 from ...round import DeviceRound, default_capacity
 from ...state import DeviceStream, FlatState, ShardGroup
+from ...utils.optimizer.adaptive import MODES as _ADAPTIVE_MODES
 from .model_adapter_base import ModelAdapterBase
+
+#: the optimizer modes whose server step set_weights() hands to update_round_gradient
+_STEP_MODES = ("fed-yogi", "q-fedavg") + tuple(_ADAPTIVE_MODES)
 
 
 _EGRESS_IDS = itertools.count(1)
@@ -459,7 +463,7 @@ class TorchModelAdapter(ModelAdapterBase):
             self._pack_values(list(weights), cur_f, cur_s)
             self._mean_f, self._mean_s, self._mean_valid = cur_f, cur_s, True
             opt = self.optimizer
-            if opt is not None and is_aggregator and getattr(opt, "mode", None) in ("fed-yogi", "q-fedavg"):
+            if opt is not None and is_aggregator and getattr(opt, "mode", None) in _STEP_MODES:
                 opt.update_round_gradient(last, FlatState(L, cur_f, cur_s), self, client_training_results)
                 return
             nf, ns = self._scratch_buffers()
@@ -1041,13 +1045,15 @@ class TorchModelAdapter(ModelAdapterBase):
 
     def _round_exposes_device_state(self) -> bool:
         """Whether a round leaves device buffers a caller can read through the public API — the FedYoGi optimizer's
-        ``m_t`` / ``v_t`` (device views, yogi.py's reference attributes) — so the caller's stream must be ordered
-        after the round (DeviceStream.joined).  Otherwise every public reader of the round's results is ordered
+        ``m_t`` / ``v_t`` (device views, yogi.py's reference attributes), or those of any gradient controller that
+        sets ``exposes_device_state`` (FedAdam, FedAdagrad, FedAvgM) — so the caller's stream must be ordered after
+        the round (DeviceStream.joined).  Otherwise every public reader of the round's results is ordered
         by the adapter itself (get_weights / egress wait on the round's event, model_weights reads on the adapter's
         stream), and the join — a hipStreamWaitEvent on a kernel still running, 5 us against 0.5 us on an idle one
         (profiles/r06_launch_api_probe.log), ~6 % of config 1's round — is skipped."""
         opt = self.optimizer
-        return opt is not None and getattr(opt, "mode", None) == "fed-yogi"
+        ctl = getattr(opt, "gradient_controller", None) if opt is not None else None
+        return bool(getattr(ctl, "exposes_device_state", False))
 
     def _take_commit_event(self):
         """The event ``_commit_scratch`` recorded for the round just applied (after all of its work on the
@@ -1085,6 +1091,19 @@ class TorchModelAdapter(ModelAdapterBase):
             kx.yogi_step(mean_f, last.f32, y.m, y.v, out_f, L.P, init=not y.initialized, **y.fp32_hparams())
             y.step_side(self._mean_s, last.side, model=out_s)
             y.initialized = True
+            self._mean_valid = True
+        elif mode in _ADAPTIVE_MODES:
+            # FedAdam / FedAdagrad / FedAvgM (utils/optimizer/adaptive.py): the same two passes — the mean into its
+            # own buffer, then one streaming step (fso_step) into the scratch model.  The int64 entries have no
+            # gradient: they take the mean, as a round without a server step writes them (model_side=out_s)
+            last = self._snapshot()
+            o = opt.gradient_controller
+            o.bind(L, self.device)
+            if self._mean_f is None or self._mean_f is last.f32 or self._mean_f is out_f:
+                self._mean_f = torch.zeros(L.ld, dtype=torch.float32, device=self.device)
+            mean_f = self._mean_f
+            rnd.finalize_mean(denom32, denom64, out=mean_f, cur_side=self._mean_s, model_side=out_s)
+            o.step(mean_f, last.f32, out_f, L.P)
             self._mean_valid = True
         elif mode == "q-fedavg":
             raise RuntimeError("q-fedavg optimizer but the round was not staged as q-FedAvg")

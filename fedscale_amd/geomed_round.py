@@ -25,7 +25,7 @@ distance and weight 0 in every iteration; when no upload is finite the model is 
 ``GeoMedRound`` is what ``TorchModelAdapter._apply_round`` and the aggregator mixins use of ``DeviceRound``, over the
 ordinary fp32 ``ClientStaging``.  All K rows must be resident: a round larger than the staging capacity is refused
 when it begins (there is no chunk folding).  Opt-in (``TorchModelAdapter.begin_round(geomed=...)``,
-``DeviceAggregatorMixin.device_geomed``); FedAvg and — as the median followed by the existing YoGi step — fed-yogi.
+``DeviceAggregatorMixin.device_geomed``); FedAvg and — as the median followed by the existing YoGi step — fed-yogi, and likewise fed-adam, fed-adagrad and fed-avgm.
 Norm clipping, trimming, Krum, 16-bit, MXFP8 and top-k uploads, cohort signatures, sharded layouts, FedBuff and
 q-FedAvg are refused.
 """

@@ -8,7 +8,7 @@ uploads, bit for bit.  This is NOT what the reference's numpy lines would do wit
 (aggregator.py:500-507 would chain in float16).  The int64 side table travels and reduces as in ``DeviceRound``.
 
 Opt-in (``TorchModelAdapter(upload_dtype=...)``); FedAvg, FedBuff and — as the mean followed by the existing YoGi
-step — fed-yogi.  q-FedAvg, sharded models, client-sharded ranks and cohort signatures are refused.
+step — fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  q-FedAvg, sharded models, client-sharded ranks and cohort signatures are refused.
 """
 from __future__ import annotations
 

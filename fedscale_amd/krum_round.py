@@ -19,7 +19,7 @@ is never kept; when no upload has a finite score the model is left as it was.
 ordinary fp32 ``ClientStaging``.  The distances need all K rows resident: a round larger than the staging capacity is
 refused when it begins (there is no chunk folding).  Opt-in (``TorchModelAdapter.begin_round(krum=...)``,
 ``DeviceAggregatorMixin.device_krum``); FedAvg and — as the selected mean followed by the existing YoGi step —
-fed-yogi.  Norm clipping, trimming, 16-bit, MXFP8 and top-k uploads, cohort signatures, sharded layouts, FedBuff and
+fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  Norm clipping, trimming, 16-bit, MXFP8 and top-k uploads, cohort signatures, sharded layouts, FedBuff and
 q-FedAvg are refused.
 """
 from __future__ import annotations

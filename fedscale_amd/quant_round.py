@@ -11,7 +11,7 @@ against the round's snapshot of ``L``: new model = L + chain / K.  The int64 sid
 ``DeviceRound``.
 
 Opt-in (``TorchModelAdapter(upload_quant="mxfp8")``); FedAvg and — as the mean followed by the existing YoGi step —
-fed-yogi.  FedBuff (a stale client's base is not this round's ``L``), q-FedAvg, 16-bit uploads, sharded models,
+fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  FedBuff (a stale client's base is not this round's ``L``), q-FedAvg, 16-bit uploads, sharded models,
 client-sharded ranks, cohort signatures, clip and trim are refused.
 """
 from __future__ import annotations

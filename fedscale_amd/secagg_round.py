@@ -17,7 +17,7 @@ deployment's protocol: the caller supplies 256-bit keys and says which are added
 graph (complete, k-regular, ring) works (INTEGRATION.md, "Secure aggregation").
 
 Opt-in (``TorchModelAdapter(upload_secagg=SecAggSpec(...))``); FedAvg and — as the mean followed by the existing YoGi
-step — fed-yogi.  FedBuff, q-FedAvg, clip, trim, Krum, geometric median, 16-bit, MXFP8 and top-k uploads, cohort
+step — fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  FedBuff, q-FedAvg, clip, trim, Krum, geometric median, 16-bit, MXFP8 and top-k uploads, cohort
 signatures, sharded layouts and client-sharded ranks are refused: each of them needs individual uploads, which is what
 secure aggregation hides.
 """

@@ -12,7 +12,7 @@ the round's snapshot of ``L``: new model = L + chain / K.  The int64 side table 
 ``DeviceRound``.
 
 Opt-in (``TorchModelAdapter(upload_sign="sign1")``); FedAvg and — as the mean followed by the existing YoGi step —
-fed-yogi.  FedBuff (a stale client's base is not this round's ``L``), q-FedAvg, the other upload formats, sharded
+fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  FedBuff (a stale client's base is not this round's ``L``), q-FedAvg, the other upload formats, sharded
 models, client-sharded ranks, cohort signatures, clip, trim, Krum, geometric-median and secure-aggregation rounds are
 refused.
 """

@@ -15,7 +15,7 @@ row of device tensors is checked on the device without a synchronisation (``fs_c
 contributes nothing to the chain, the mean still divides by K, and ``SparseRound.rejected()`` counts such rows.
 
 Opt-in (``TorchModelAdapter(upload_topk=density)``); FedAvg and — as the mean followed by the existing YoGi step —
-fed-yogi.  FedBuff (a stale client's base is not this round's ``L``), q-FedAvg, 16-bit uploads, MXFP8 uploads,
+fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  FedBuff (a stale client's base is not this round's ``L``), q-FedAvg, 16-bit uploads, MXFP8 uploads,
 sharded models, client-sharded ranks, cohort signatures, clip and trim are refused.
 """
 from __future__ import annotations

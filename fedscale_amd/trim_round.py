@@ -16,7 +16,7 @@ table takes plain FedAvg's path with denominator K.  With t = 0 the round is pla
 ordinary fp32 ``ClientStaging``.  The selection needs all K rows resident: a round larger than the staging capacity
 is refused when it begins (there is no chunk folding).  Opt-in (``TorchModelAdapter.begin_round(trim=...)``,
 ``DeviceAggregatorMixin.device_trim``); FedAvg and — as the trimmed mean followed by the existing YoGi step —
-fed-yogi.  Norm clipping, 16-bit uploads, cohort signatures, sharded layouts, FedBuff and q-FedAvg are refused.
+fed-yogi, fed-adam, fed-adagrad or fed-avgm (the mean, then the server step).  Norm clipping, 16-bit uploads, cohort signatures, sharded layouts, FedBuff and q-FedAvg are refused.
 """
 from __future__ import annotations
 

@@ -27,6 +27,10 @@ def _f32(x: float) -> float:
 
 
 class YoGi:
+    #: a round leaves device state (m_t / v_t) a caller can read: the adapter orders the caller's stream after the
+    #: round (TorchModelAdapter._round_exposes_device_state)
+    exposes_device_state = True
+
     def __init__(self, eta=1e-2, tau=1e-3, beta=0.9, beta2=0.99):
         self.eta = eta
         self.tau = tau
