@@ -71,6 +71,10 @@ inline int fa_host_mapped(const void* p) {
 class DevScope {
  public:
   DevScope(const char* what, fa_stream_t stream, const void* anchor) : what_(what), saved_(fa_t_dev) {
+    // HIP keeps a failed call's error for the thread until somebody reads it.  One left by a call made before this
+    // entry point (by anyone: a refused hipHostRegister of the caller's, say) is not a launch failure of ours:
+    // clear it, so that check_launch reports this call's launches only.
+    (void)hipGetLastError();
     if (hipGetDevice(&prev_) != hipSuccess) {
       (void)hipGetLastError();
       rc_ = err(FA_E_HIP, what, "no current HIP device", -1, -1);

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import host_register
 from tests.golden_io import Scenario, StateDictModule, assert_state_close, assert_state_equal, scenario_names
 
 pytestmark = pytest.mark.gpu
@@ -678,6 +679,8 @@ def test_registered_payload_ingress_is_bit_exact(gpu_device, parts):
     of the large arrays straight out of the payload (RegisteredUpload, fa_h2d_pieces); small entries and int64
     entries come from the pinned row.  Mixed with plain dict uploads (the gather path) in the same round, over
     chunk folds: the model is the oracle's FedAvg mean bit for bit, and every registration is released."""
+    if not host_register.supported():
+        pytest.skip(host_register.REASON)
     from fedscale_amd import ingress
     from fedscale_amd.cloud.aggregation.aggregator import DeviceAggregator
     from fedscale_amd.cloud.internal.sharded_model_adapter import ShardedModelAdapter
