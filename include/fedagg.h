@@ -165,6 +165,8 @@ int64_t fa_qfed_launches(int64_t ld, int64_t P, int32_t chain);
  *   g_k = (last - x[k]) / lr                      (fp32 true division)
  *   delta = FA_ACCUMULATE ? delta + alpha_k*g_0 : alpha_0*g_0; delta = delta + alpha_k*g_k ...
  *   sqnorm[k] += sum_p fp32(g_k[p]^2)              (accumulated in fp64, deterministic order)
+ *     The sum runs over the 4*ceil(P/4) columns the kernel reads; the bucket's zero padding keeps the last < 4 of
+ *     them at zero.
  *   chain (optional, may be NULL) = FA_ACCUMULATE ? chain + x[0] : x[0]; chain = chain + x[k] ...
  * Replaces: the per-client loop of optimizers.py:73-98 (client results retained at aggregator.py:466-467)
  * and, through `chain`, the FedAvg sum the reference computes on the same inputs (aggregator.py:497-503,

@@ -4,9 +4,9 @@ count, each against the oracle's flat restatement of the reference arithmetic.
 
 * FedAvg / FedBuff (aggregator.py:497-507, async_aggregator.py:125-135): bit-exact, in one call or split into
   two chunks that continue the chain (DeviceRound's chunk folding), from device rows or from pinned host rows.
-* q-FedAvg phase 1 (optimizers.py:82-98): the delta chain and the FedAvg chain bit-exact, the per-client squared
-  norms within 5e-7 relative: the kernel sums fp32 partials of 4 (8 in chain launches) squares in fp64 in a fixed
-  order, so a norm of a few elements carries up to 7 fp32 roundings (the reference's own torch CPU order is
+* q-FedAvg phase 1 (optimizers.py:82-98): the delta chain and the FedAvg chain bit-exact, and the per-client squared
+  norms bit-exact against the kernel's own summation order restated in numpy (tests/qfed_fixtures.py: fp32 partials
+  of 4, in chain launches 8, squares summed in fp64 in a fixed order; the reference's own torch CPU order is
   implementation-defined); with the chain fused or not, in one call or two.
 Inputs are seeded and sized so the whole file runs in seconds; the shapes include P below one strip, P not a
 multiple of 4, ld with padding, K = 1, and column counts just past a strip or a tile."""
@@ -17,6 +17,7 @@ from hypothesis import HealthCheck, example, given, settings
 from hypothesis import strategies as st
 
 from oracle.cpu_reference import fedavg_flat, fedbuff_flat
+from tests import qfed_fixtures
 
 pytestmark = pytest.mark.gpu
 
@@ -90,13 +91,15 @@ def test_qfed_accumulate_matches_oracle(gpu_device, shape, chain, split, q, lr):
     alpha = np.array([np.float32(np.float_power(v + 1e-10, q)) for v in losses], dtype=np.float32)
     # optimizers.py:82-93 in fp32, arrival order; aggregator.py:497-503's chain of the same uploads
     d = c = None
-    sq_ref = np.zeros(K)
+    h = split % K
+    parts = [(0, K)] if h == 0 else [(0, h), (h, K)]
+    sq_ref = np.concatenate([qfed_fixtures.accumulate(xh[k0:k1], L, alpha[k0:k1], lr, chain, P=P)[2]
+                             for k0, k1 in parts])  # the norms in the kernel's own order, per call
     for k in range(K):
         g = (L[:P] - xh[k, :P]) / np.float32(lr)
         t = alpha[k] * g
         d = t if d is None else d + t
         c = xh[k, :P] if c is None else c + xh[k, :P]
-        sq_ref[k] = np.sum((g * g).astype(np.float64))
     x = torch.from_numpy(xh).cuda()
     Ld = torch.from_numpy(L).cuda()
     al = torch.from_numpy(alpha).cuda()
@@ -105,8 +108,6 @@ def test_qfed_accumulate_matches_oracle(gpu_device, shape, chain, split, q, lr):
     ch = torch.full((cols,), float("nan"), device="cuda") if chain else None
     sq = torch.zeros(K, dtype=torch.float64, device="cuda")  # fa_qfed_accumulate adds into sqnorm (fedagg.h)
     ws = kx.qfed_workspace(K, "cuda", ld, P)
-    h = split % K
-    parts = [(0, K)] if h == 0 else [(0, h), (h, K)]
     for i, (k0, k1) in enumerate(parts):
         kx.qfed_accumulate(x[k0:k1], k1 - k0, P, last=Ld, alpha=al[k0:k1], lr=lr, delta=delta, sqnorm=sq[k0:k1],
                            workspace=ws, accumulate=i > 0, chain=ch)
@@ -114,7 +115,7 @@ def test_qfed_accumulate_matches_oracle(gpu_device, shape, chain, split, q, lr):
     np.testing.assert_array_equal(delta[:P].cpu().numpy(), d)
     if chain:
         np.testing.assert_array_equal(ch[:P].cpu().numpy(), c)
-    np.testing.assert_allclose(sq.cpu().numpy(), sq_ref, rtol=5e-7, atol=0)
+    np.testing.assert_array_equal(sq.cpu().numpy(), sq_ref)
 
 
 @settings(max_examples=60, deadline=None, derandomize=True,
