@@ -111,6 +111,14 @@ class DeviceAggregatorMixin:
     #: the 1-bit encoding's fidelity independent of the update's distribution; the round rotates its chain back once
     #: (fedscale_amd/rotate_round.py).  Refused wherever device_upload_sign is, and without it
     device_upload_rotate = None
+    #: opt-in: a rank in 1..64 — the executors upload, for every weight matrix worth factoring, rank-r factors of their
+    #: update against the weights they were sent for this round (fedscale_amd/cloud/execution/lowrank_upload.py: lossy
+    #: on the wire, exact from there on; error feedback is the executor's state); staged in HBM at r (O + I) floats
+    #: per O x I matrix and multiplied out on the matrix unit (fedscale_amd/lowrank_round.py).  FedAvg, fed-yogi,
+    #: fed-adam, fed-adagrad and fed-avgm; q-FedAvg, device_shards, the other upload formats, device_clip_norm,
+    #: device_trim, device_krum, device_geomed, device_upload_secagg, the async and the cohort mixin's signatures are
+    #: refused with it
+    device_upload_lowrank = None
     #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
     #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
     #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
@@ -320,6 +328,8 @@ class DeviceAggregatorMixin:
                 kw["upload_sign"] = self.device_upload_sign
             if self.device_upload_rotate is not None:
                 kw["upload_rotate"] = self.device_upload_rotate
+            if self.device_upload_lowrank is not None:
+                kw["upload_lowrank"] = self.device_upload_lowrank
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
@@ -335,6 +345,8 @@ class DeviceAggregatorMixin:
                 kw["upload_sign"] = self.device_upload_sign
             if self.device_upload_rotate is not None:
                 kw["upload_rotate"] = self.device_upload_rotate
+            if self.device_upload_lowrank is not None:
+                kw["upload_lowrank"] = self.device_upload_lowrank
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
@@ -558,6 +570,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_rotate)
+        if self.device_upload_lowrank is not None:
+            from ...lowrank_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
+                         self.device_upload_lowrank)
         if self.device_upload_secagg is not None:
             from ...secagg_round import refuse
 

@@ -216,6 +216,27 @@ def _rebuild_with_upload_rotate(cls, model, optimizer, fmt, rot):
     return cls(model, optimizer, upload_sign=fmt, upload_rotate=rot)
 
 
+def _takes_upload_lowrank(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_lowrank`` — wired as
+    ``_takes_upload_topk`` wires its option: set on the instance before the constructor's body runs (which refuses
+    what it does not combine with); an adapter that has it pickles through ``_rebuild_with_upload_lowrank``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_lowrank: Optional[int] = None, **kw):
+        if upload_lowrank is not None:
+            from ..execution.lowrank_upload import check_rank
+
+            self.upload_lowrank = check_rank(upload_lowrank)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_lowrank(cls, model, optimizer, rank):
+    """Unpickle an adapter with ``upload_lowrank`` (``TorchModelAdapter.__reduce__``)."""
+    return cls(model, optimizer, upload_lowrank=rank)
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -239,9 +260,13 @@ class TorchModelAdapter(ModelAdapterBase):
     #: "rht4096" (with ``upload_sign``): the clients rotate their update by a seeded 4096-point block Hadamard
     #: transform before the sign encoder sees it, and the round rotates its chain back once (None: no rotation)
     upload_rotate = None
+    #: a rank in 1..64: the clients upload rank-r factors of their update's weight matrices against the round's model,
+    #: multiplied out on the device's matrix unit (None: whole weights)
+    upload_lowrank = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_lowrank
     @_takes_upload_rotate
     @_takes_upload_sign
     @_takes_upload_secagg
@@ -271,7 +296,11 @@ class TorchModelAdapter(ModelAdapterBase):
         ``upload_rotate`` (keyword only, taken by ``_takes_upload_rotate``; "rht4096"; needs ``upload_sign``): clients
         rotate their update by the seeded block Hadamard transform of include/fedrotate.h before it is encoded
         (fedscale_amd/cloud/execution/rotate_upload.py); ``begin_round`` then returns a ``RotatedSignRound`` over a
-        ``RotatedSignStaging`` (fedscale_amd/rotate_round.py)."""
+        ``RotatedSignStaging`` (fedscale_amd/rotate_round.py).
+        ``upload_lowrank`` (keyword only, taken by ``_takes_upload_lowrank``; a rank in 1..64; None: whole weights):
+        clients upload, for every weight matrix worth factoring, rank-r factors of their update against the weights
+        they were sent for this round (fedscale_amd/cloud/execution/lowrank_upload.py); ``begin_round`` then returns
+        a ``LowRankRound`` over a ``LowRankStaging`` (fedscale_amd/lowrank_round.py)."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -342,6 +371,24 @@ class TorchModelAdapter(ModelAdapterBase):
             from ...rotate_round import refuse as refuse_r
 
             raise refuse_r("no upload_sign (the rotation goes around the 1-bit sign encoder)", rot)
+        lowrank = self.__dict__.get("upload_lowrank")  # set by _takes_upload_lowrank before this body runs
+        if lowrank is not None:
+            from ...lowrank_round import refuse as refuse_l
+
+            if self.upload_dtype is not None:
+                raise refuse_l(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)", lowrank)
+            if self.upload_quant is not None:
+                raise refuse_l(f"upload_quant={self.upload_quant!r} (MXFP8 delta uploads)", lowrank)
+            if topk is not None:
+                raise refuse_l(f"upload_topk={topk!r} (top-k sparse delta uploads)", lowrank)
+            if self.__dict__.get("upload_secagg") is not None:
+                raise refuse_l("upload_secagg (secure-aggregation uploads)", lowrank)
+            if sign is not None:
+                raise refuse_l(f"upload_sign={sign!r} (1-bit sign delta uploads)", lowrank)
+            if shards is not None and shards.world != 1:
+                raise refuse_l("a sharded model or client-sharded ranks (ShardGroup)", lowrank)
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse_l("the q-fedavg server optimizer", lowrank)
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -657,6 +704,9 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if getattr(self, "upload_lowrank", None) is not None:
+            return (_rebuild_with_upload_lowrank, (self.__class__, self.get_model(), self.optimizer,
+                                                   self.upload_lowrank))
         if getattr(self, "upload_secagg", None) is not None:
             return (_rebuild_with_upload_secagg, (self.__class__, self.get_model(), self.optimizer,
                                                   self.upload_secagg))
@@ -702,6 +752,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if krum is not None:
             krum = self._check_krum(policy, signatures, clip, trim, krum)
             krum.counts(K)  # (counts the round cannot take are refused here, with nothing allocated)
+        if getattr(self, "upload_lowrank", None) is not None:
+            return self._begin_lowrank_round(K, policy, capacity, signatures, clip, trim)
         if getattr(self, "upload_sign", None) is not None:
             return self._begin_sign_round(K, policy, capacity, signatures, clip, trim)
         if getattr(self, "upload_topk", None) is not None:
@@ -825,6 +877,8 @@ class TorchModelAdapter(ModelAdapterBase):
             raise refuse("clip (a norm-clipped round)")
         if trim is not None:
             raise refuse("trim (a trimmed-mean round)")
+        if getattr(self, "upload_lowrank", None) is not None:
+            raise refuse(f"upload_lowrank={self.upload_lowrank!r} (low-rank delta uploads)")
         if getattr(self, "upload_sign", None) is not None:
             raise refuse(f"upload_sign={self.upload_sign!r} (1-bit sign delta uploads)")
         if getattr(self, "upload_topk", None) is not None:
@@ -857,6 +911,8 @@ class TorchModelAdapter(ModelAdapterBase):
             raise refuse("trim (a trimmed-mean round)")
         if krum is not None:
             raise refuse("krum (a Multi-Krum round)")
+        if getattr(self, "upload_lowrank", None) is not None:
+            raise refuse(f"upload_lowrank={self.upload_lowrank!r} (low-rank delta uploads)")
         if getattr(self, "upload_sign", None) is not None:
             raise refuse(f"upload_sign={self.upload_sign!r} (1-bit sign delta uploads)")
         if getattr(self, "upload_topk", None) is not None:
@@ -993,6 +1049,39 @@ class TorchModelAdapter(ModelAdapterBase):
             self.staging = SignStaging(self.layout, self.device, want, dstream=self.dstream)
         return SignRound(self.layout, self.device, K, policy, staging=self.staging, last_f32=self._snapshot().f32,
                          capacity=want, dstream=self.dstream)
+
+    def _begin_lowrank_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim):
+        """``begin_round`` of an adapter with ``upload_lowrank``: a ``LowRankRound`` over a ``LowRankStaging`` whose
+        default capacity is computed from rows of factors.  The combinations the low-rank path does not take are
+        refused here, before a device is touched (krum and geomed by their own checks, above)."""
+        from ...lowrank_round import LowRankRound, LowRankStaging, default_capacity_lowrank, layout_dims, refuse
+
+        r = self.upload_lowrank
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)", r)
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)", r)
+        if signatures:
+            raise refuse("cohort signatures", r)
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round", r)
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)", r)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            from ...kernels_lowrank import row_layout
+
+            want = default_capacity_lowrank(self.layout, K, row_layout(r, layout_dims(self.layout, r))[0],
+                                            self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = LowRankStaging(self.layout, self.device, want, r, dstream=self.dstream)
+        return LowRankRound(self.layout, self.device, K, policy, staging=self.staging,
+                            last_f32=self._snapshot().f32, capacity=want, dstream=self.dstream)
 
     def _begin_secagg_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
                             geomed):
@@ -1137,6 +1226,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "upload_topk", None) is not None:  # a SparseRound finishes through fcl_finish
             return False
         if getattr(rnd, "upload_sign", None) is not None:  # a SignRound finishes through fcl_finish
+            return False
+        if getattr(rnd, "upload_lowrank", None) is not None:  # a LowRankRound finishes through fcl_finish
             return False
         if getattr(rnd, "upload_secagg", None) is not None:  # a SecAggRound finishes through fsa_finish
             return False
