@@ -119,6 +119,14 @@ class DeviceAggregatorMixin:
     #: device_trim, device_krum, device_geomed, device_upload_secagg, the async and the cohort mixin's signatures are
     #: refused with it
     device_upload_lowrank = None
+    #: opt-in: a ``VoteSpec`` or a bare server learning rate — the executors upload only the sign bits of their update
+    #: against the weights they were sent for this round (fedscale_amd/cloud/execution/vote_upload.py: no scales, so
+    #: every client has exactly one vote per coordinate whatever it sends); staged in HBM at 1/8 byte per parameter,
+    #: tallied exactly and closed by the majority vote (fedscale_amd/vote_round.py).  FedAvg, fed-yogi, fed-adam,
+    #: fed-adagrad and fed-avgm; q-FedAvg, device_shards, the other upload formats, device_clip_norm, device_trim,
+    #: device_krum, device_geomed, device_upload_secagg, the async and the cohort mixin's signatures are refused
+    #: with it
+    device_upload_vote = None
     #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
     #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
     #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
@@ -330,6 +338,8 @@ class DeviceAggregatorMixin:
                 kw["upload_rotate"] = self.device_upload_rotate
             if self.device_upload_lowrank is not None:
                 kw["upload_lowrank"] = self.device_upload_lowrank
+            if self.device_upload_vote is not None:
+                kw["upload_vote"] = self.device_upload_vote
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
@@ -347,6 +357,8 @@ class DeviceAggregatorMixin:
                 kw["upload_rotate"] = self.device_upload_rotate
             if self.device_upload_lowrank is not None:
                 kw["upload_lowrank"] = self.device_upload_lowrank
+            if self.device_upload_vote is not None:
+                kw["upload_vote"] = self.device_upload_vote
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
@@ -575,6 +587,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_lowrank)
+        if self.device_upload_vote is not None:
+            from ...vote_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
+                         self.device_upload_vote)
         if self.device_upload_secagg is not None:
             from ...secagg_round import refuse
 

@@ -84,7 +84,7 @@ class ShardedModelAdapter(TorchModelAdapter):
                  transport: Optional[str] = None, upload_dtype: Optional[str] = None,
                  upload_quant: Optional[str] = None, upload_topk: Optional[float] = None, upload_secagg=None,
                  upload_sign: Optional[str] = None, upload_rotate: Optional[str] = None,
-                 upload_lowrank: Optional[int] = None):
+                 upload_lowrank: Optional[int] = None, upload_vote=None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
@@ -113,6 +113,10 @@ class ShardedModelAdapter(TorchModelAdapter):
             from ...lowrank_round import refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_lowrank)
+        if upload_vote is not None:  # majority-vote sign uploads (fedscale_amd/vote_round.py): likewise
+            from ...vote_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_vote)
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -237,6 +237,27 @@ def _rebuild_with_upload_lowrank(cls, model, optimizer, rank):
     return cls(model, optimizer, upload_lowrank=rank)
 
 
+def _takes_upload_vote(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_vote`` — wired as
+    ``_takes_upload_lowrank`` wires its option: set on the instance before the constructor's body runs (which refuses
+    what it does not combine with); an adapter that has it pickles through ``_rebuild_with_upload_vote``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_vote=None, **kw):
+        if upload_vote is not None:
+            from ..execution.vote_upload import VoteSpec
+
+            self.upload_vote = VoteSpec.of(upload_vote)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_vote(cls, model, optimizer, spec):
+    """Unpickle an adapter with ``upload_vote`` (``TorchModelAdapter.__reduce__``)."""
+    return cls(model, optimizer, upload_vote=spec)
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -263,9 +284,13 @@ class TorchModelAdapter(ModelAdapterBase):
     #: a rank in 1..64: the clients upload rank-r factors of their update's weight matrices against the round's model,
     #: multiplied out on the device's matrix unit (None: whole weights)
     upload_lowrank = None
+    #: a ``VoteSpec`` (or a bare server learning rate): the clients upload only the sign bits of their update against
+    #: the round's model and the new model is their majority vote (None: whole weights)
+    upload_vote = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_vote
     @_takes_upload_lowrank
     @_takes_upload_rotate
     @_takes_upload_sign
@@ -300,7 +325,11 @@ class TorchModelAdapter(ModelAdapterBase):
         ``upload_lowrank`` (keyword only, taken by ``_takes_upload_lowrank``; a rank in 1..64; None: whole weights):
         clients upload, for every weight matrix worth factoring, rank-r factors of their update against the weights
         they were sent for this round (fedscale_amd/cloud/execution/lowrank_upload.py); ``begin_round`` then returns
-        a ``LowRankRound`` over a ``LowRankStaging`` (fedscale_amd/lowrank_round.py)."""
+        a ``LowRankRound`` over a ``LowRankStaging`` (fedscale_amd/lowrank_round.py).
+        ``upload_vote`` (keyword only, taken by ``_takes_upload_vote``; a ``VoteSpec`` or a bare server learning rate;
+        None: whole weights): clients upload only the sign bits of their update against the weights they were sent
+        for this round (fedscale_amd/cloud/execution/vote_upload.py); ``begin_round`` then returns a ``VoteRound``
+        over a ``VoteStaging`` (fedscale_amd/vote_round.py), whose new model is the majority vote."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -389,6 +418,26 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse_l("a sharded model or client-sharded ranks (ShardGroup)", lowrank)
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse_l("the q-fedavg server optimizer", lowrank)
+        vote = self.__dict__.get("upload_vote")  # set by _takes_upload_vote before this body runs
+        if vote is not None:
+            from ...vote_round import refuse as refuse_v
+
+            if self.upload_dtype is not None:
+                raise refuse_v(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)", vote)
+            if self.upload_quant is not None:
+                raise refuse_v(f"upload_quant={self.upload_quant!r} (MXFP8 delta uploads)", vote)
+            if topk is not None:
+                raise refuse_v(f"upload_topk={topk!r} (top-k sparse delta uploads)", vote)
+            if self.__dict__.get("upload_secagg") is not None:
+                raise refuse_v("upload_secagg (secure-aggregation uploads)", vote)
+            if sign is not None:
+                raise refuse_v(f"upload_sign={sign!r} (1-bit sign delta uploads)", vote)
+            if lowrank is not None:
+                raise refuse_v(f"upload_lowrank={lowrank!r} (low-rank delta uploads)", vote)
+            if shards is not None and shards.world != 1:
+                raise refuse_v("a sharded model or client-sharded ranks (ShardGroup)", vote)
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse_v("the q-fedavg server optimizer", vote)
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -704,6 +753,8 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if getattr(self, "upload_vote", None) is not None:
+            return (_rebuild_with_upload_vote, (self.__class__, self.get_model(), self.optimizer, self.upload_vote))
         if getattr(self, "upload_lowrank", None) is not None:
             return (_rebuild_with_upload_lowrank, (self.__class__, self.get_model(), self.optimizer,
                                                    self.upload_lowrank))
@@ -746,6 +797,8 @@ class TorchModelAdapter(ModelAdapterBase):
         (fedscale_amd/geomed_round.py), which needs all K uploads resident."""
         if getattr(self, "upload_secagg", None) is not None:
             return self._begin_secagg_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
+        if getattr(self, "upload_vote", None) is not None:
+            return self._begin_vote_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
         if geomed is not None:
             geomed = self._check_geomed(policy, signatures, clip, trim, krum, geomed)
             geomed.resolve(K)  # (a K the round cannot take is refused here, with nothing allocated)
@@ -1083,6 +1136,41 @@ class TorchModelAdapter(ModelAdapterBase):
         return LowRankRound(self.layout, self.device, K, policy, staging=self.staging,
                             last_f32=self._snapshot().f32, capacity=want, dstream=self.dstream)
 
+    def _begin_vote_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
+                          geomed):
+        """``begin_round`` of an adapter with ``upload_vote``: a ``VoteRound`` over a ``VoteStaging`` whose default
+        capacity is computed from rows of 1/8 byte per parameter.  The combinations the majority-vote path does not
+        take are refused here, before a device is touched."""
+        from ...vote_round import VoteRound, VoteStaging, default_capacity_vote, refuse
+
+        spec = self.upload_vote
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)", spec)
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)", spec)
+        if krum is not None:
+            raise refuse("krum (a Multi-Krum round)", spec)
+        if geomed is not None:
+            raise refuse("geomed (a geometric-median round)", spec)
+        if signatures:
+            raise refuse("cohort signatures", spec)
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round", spec)
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)", spec)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            want = default_capacity_vote(self.layout, K, self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = VoteStaging(self.layout, self.device, want, dstream=self.dstream)
+        return VoteRound(self.layout, self.device, K, policy, spec, staging=self.staging,
+                         last_f32=self._snapshot().f32, capacity=want, dstream=self.dstream)
+
     def _begin_secagg_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
                             geomed):
         """``begin_round`` of an adapter with ``upload_secagg``: a ``SecAggRound`` over a ``MaskedStaging`` whose
@@ -1228,6 +1316,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "upload_sign", None) is not None:  # a SignRound finishes through fcl_finish
             return False
         if getattr(rnd, "upload_lowrank", None) is not None:  # a LowRankRound finishes through fcl_finish
+            return False
+        if getattr(rnd, "upload_vote", None) is not None:  # a VoteRound finishes through fvt_finish
             return False
         if getattr(rnd, "upload_secagg", None) is not None:  # a SecAggRound finishes through fsa_finish
             return False
