@@ -127,6 +127,13 @@ class DeviceAggregatorMixin:
     #: device_krum, device_geomed, device_upload_secagg, the async and the cohort mixin's signatures are refused
     #: with it
     device_upload_vote = None
+    #: opt-in: "mxfp4" — the executors upload their update against the weights they were sent for this round,
+    #: quantised to MXFP4 (fedscale_amd/cloud/execution/quant4_upload.py: lossy on the wire, exact from there on; error
+    #: feedback is the executor's state); staged in HBM at 17/32 byte per parameter and reduced in fp32
+    #: (fedscale_amd/quant4_round.py).  FedAvg, fed-yogi, fed-adam, fed-adagrad and fed-avgm; q-FedAvg, device_shards,
+    #: the other upload formats, device_clip_norm, device_trim, device_krum, device_geomed, device_upload_secagg, the
+    #: async and the cohort mixin's signatures are refused with it
+    device_upload_fp4 = None
     #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
     #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
     #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
@@ -340,6 +347,8 @@ class DeviceAggregatorMixin:
                 kw["upload_lowrank"] = self.device_upload_lowrank
             if self.device_upload_vote is not None:
                 kw["upload_vote"] = self.device_upload_vote
+            if self.device_upload_fp4 is not None:
+                kw["upload_fp4"] = self.device_upload_fp4
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
@@ -359,6 +368,8 @@ class DeviceAggregatorMixin:
                 kw["upload_lowrank"] = self.device_upload_lowrank
             if self.device_upload_vote is not None:
                 kw["upload_vote"] = self.device_upload_vote
+            if self.device_upload_fp4 is not None:
+                kw["upload_fp4"] = self.device_upload_fp4
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
@@ -592,6 +603,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_vote)
+        if self.device_upload_fp4 is not None:
+            from ...quant4_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
+                         self.device_upload_fp4)
         if self.device_upload_secagg is not None:
             from ...secagg_round import refuse
 

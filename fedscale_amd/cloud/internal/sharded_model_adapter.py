@@ -84,7 +84,8 @@ class ShardedModelAdapter(TorchModelAdapter):
                  transport: Optional[str] = None, upload_dtype: Optional[str] = None,
                  upload_quant: Optional[str] = None, upload_topk: Optional[float] = None, upload_secagg=None,
                  upload_sign: Optional[str] = None, upload_rotate: Optional[str] = None,
-                 upload_lowrank: Optional[int] = None, upload_vote=None):
+                 upload_lowrank: Optional[int] = None, upload_vote=None,
+                 upload_fp4: Optional[str] = None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
@@ -117,6 +118,10 @@ class ShardedModelAdapter(TorchModelAdapter):
             from ...vote_round import refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_vote)
+        if upload_fp4 is not None:  # MXFP4 delta uploads (fedscale_amd/quant4_round.py): likewise
+            from ...quant4_round import check_format4, refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", check_format4(upload_fp4))
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -258,6 +258,27 @@ def _rebuild_with_upload_vote(cls, model, optimizer, spec):
     return cls(model, optimizer, upload_vote=spec)
 
 
+def _takes_upload_fp4(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_fp4`` — wired as
+    ``_takes_upload_vote`` wires its option: set on the instance before the constructor's body runs (which refuses
+    what it does not combine with); an adapter that has it pickles through ``_rebuild_with_upload_fp4``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_fp4: Optional[str] = None, **kw):
+        if upload_fp4 is not None:
+            from ...quant4_round import check_format4
+
+            self.upload_fp4 = check_format4(upload_fp4)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_fp4(cls, model, optimizer, fmt):
+    """Unpickle an adapter with ``upload_fp4`` (``TorchModelAdapter.__reduce__``)."""
+    return cls(model, optimizer, upload_fp4=fmt)
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -287,9 +308,13 @@ class TorchModelAdapter(ModelAdapterBase):
     #: a ``VoteSpec`` (or a bare server learning rate): the clients upload only the sign bits of their update against
     #: the round's model and the new model is their majority vote (None: whole weights)
     upload_vote = None
+    #: "mxfp4": the clients upload MXFP4-quantised deltas against the round's model, 17/32 byte per parameter (None:
+    #: whole weights)
+    upload_fp4 = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_fp4
     @_takes_upload_vote
     @_takes_upload_lowrank
     @_takes_upload_rotate
@@ -329,7 +354,11 @@ class TorchModelAdapter(ModelAdapterBase):
         ``upload_vote`` (keyword only, taken by ``_takes_upload_vote``; a ``VoteSpec`` or a bare server learning rate;
         None: whole weights): clients upload only the sign bits of their update against the weights they were sent
         for this round (fedscale_amd/cloud/execution/vote_upload.py); ``begin_round`` then returns a ``VoteRound``
-        over a ``VoteStaging`` (fedscale_amd/vote_round.py), whose new model is the majority vote."""
+        over a ``VoteStaging`` (fedscale_amd/vote_round.py), whose new model is the majority vote.
+        ``upload_fp4`` (keyword only, taken by ``_takes_upload_fp4``; "mxfp4"; None: whole weights): clients upload
+        their update against the weights they were sent for this round, quantised to MXFP4
+        (fedscale_amd/cloud/execution/quant4_upload.py); ``begin_round`` then returns a ``Quant4Round`` over a
+        ``Quant4Staging`` (fedscale_amd/quant4_round.py)."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -438,6 +467,28 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse_v("a sharded model or client-sharded ranks (ShardGroup)", vote)
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse_v("the q-fedavg server optimizer", vote)
+        fp4 = self.__dict__.get("upload_fp4")  # set by _takes_upload_fp4 before this body runs
+        if fp4 is not None:
+            from ...quant4_round import refuse as refuse_4
+
+            if self.upload_dtype is not None:
+                raise refuse_4(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)", fp4)
+            if self.upload_quant is not None:
+                raise refuse_4(f"upload_quant={self.upload_quant!r} (MXFP8 delta uploads)", fp4)
+            if topk is not None:
+                raise refuse_4(f"upload_topk={topk!r} (top-k sparse delta uploads)", fp4)
+            if self.__dict__.get("upload_secagg") is not None:
+                raise refuse_4("upload_secagg (secure-aggregation uploads)", fp4)
+            if sign is not None:
+                raise refuse_4(f"upload_sign={sign!r} (1-bit sign delta uploads)", fp4)
+            if lowrank is not None:
+                raise refuse_4(f"upload_lowrank={lowrank!r} (low-rank delta uploads)", fp4)
+            if vote is not None:
+                raise refuse_4(f"upload_vote={vote!r} (majority-vote sign uploads)", fp4)
+            if shards is not None and shards.world != 1:
+                raise refuse_4("a sharded model or client-sharded ranks (ShardGroup)", fp4)
+            if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
+                raise refuse_4("the q-fedavg server optimizer", fp4)
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -753,6 +804,8 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if getattr(self, "upload_fp4", None) is not None:
+            return (_rebuild_with_upload_fp4, (self.__class__, self.get_model(), self.optimizer, self.upload_fp4))
         if getattr(self, "upload_vote", None) is not None:
             return (_rebuild_with_upload_vote, (self.__class__, self.get_model(), self.optimizer, self.upload_vote))
         if getattr(self, "upload_lowrank", None) is not None:
@@ -799,6 +852,8 @@ class TorchModelAdapter(ModelAdapterBase):
             return self._begin_secagg_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
         if getattr(self, "upload_vote", None) is not None:
             return self._begin_vote_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
+        if getattr(self, "upload_fp4", None) is not None:
+            return self._begin_fp4_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
         if geomed is not None:
             geomed = self._check_geomed(policy, signatures, clip, trim, krum, geomed)
             geomed.resolve(K)  # (a K the round cannot take is refused here, with nothing allocated)
@@ -1171,6 +1226,41 @@ class TorchModelAdapter(ModelAdapterBase):
         return VoteRound(self.layout, self.device, K, policy, spec, staging=self.staging,
                          last_f32=self._snapshot().f32, capacity=want, dstream=self.dstream)
 
+    def _begin_fp4_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
+                         geomed):
+        """``begin_round`` of an adapter with ``upload_fp4``: a ``Quant4Round`` over a ``Quant4Staging`` whose default
+        capacity is computed from rows of 17/32 byte per parameter.  The combinations the 4-bit delta path does not
+        take are refused here, before a device is touched."""
+        from ...quant4_round import Quant4Round, Quant4Staging, default_capacity4, refuse
+
+        fmt = self.upload_fp4
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)", fmt)
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)", fmt)
+        if krum is not None:
+            raise refuse("krum (a Multi-Krum round)", fmt)
+        if geomed is not None:
+            raise refuse("geomed (a geometric-median round)", fmt)
+        if signatures:
+            raise refuse("cohort signatures", fmt)
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round", fmt)
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)", fmt)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            want = default_capacity4(self.layout, K, self.device)
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = Quant4Staging(self.layout, self.device, want, dstream=self.dstream)
+        return Quant4Round(self.layout, self.device, K, policy, staging=self.staging,
+                           last_f32=self._snapshot().f32, capacity=want, dstream=self.dstream)
+
     def _begin_secagg_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
                             geomed):
         """``begin_round`` of an adapter with ``upload_secagg``: a ``SecAggRound`` over a ``MaskedStaging`` whose
@@ -1318,6 +1408,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "upload_lowrank", None) is not None:  # a LowRankRound finishes through fcl_finish
             return False
         if getattr(rnd, "upload_vote", None) is not None:  # a VoteRound finishes through fvt_finish
+            return False
+        if getattr(rnd, "upload_fp4", None) is not None:  # a Quant4Round finishes through fcl_finish
             return False
         if getattr(rnd, "upload_secagg", None) is not None:  # a SecAggRound finishes through fsa_finish
             return False
