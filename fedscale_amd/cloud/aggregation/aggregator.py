@@ -134,6 +134,14 @@ class DeviceAggregatorMixin:
     #: the other upload formats, device_clip_norm, device_trim, device_krum, device_geomed, device_upload_secagg, the
     #: async and the cohort mixin's signatures are refused with it
     device_upload_fp4 = None
+    #: opt-in: a ``SketchSpec`` (or True for its defaults) — the executors upload a Count Sketch of their update against
+    #: the weights they were sent for this round, rows x cols floats whatever the model's size, and keep no state
+    #: between rounds (fedscale_amd/cloud/execution/sketch_upload.py); the tables are averaged by fa_reduce and the
+    #: round is FetchSGD's server step: momentum and error feedback in sketch space, the k heaviest recovered columns
+    #: applied (fedscale_amd/sketch_round.py; INTEGRATION.md, "Sketched uploads").  FedAvg only: every other
+    #: gradient_policy, device_shards, the other upload formats, device_clip_norm, device_trim, device_krum,
+    #: device_geomed, device_upload_secagg, the async and the cohort mixin's signatures are refused with it
+    device_upload_sketch = None
     #: opt-in: a norm bound M (finite, > 0) — every client's update (upload minus the round's starting model, the
     #: whole fp32 bucket) is clipped to it on the device before it is averaged (fedscale_amd/clip_round.py;
     #: INTEGRATION.md, "Norm-bounded aggregation").  FedAvg and fed-yogi; q-FedAvg, device_shards,
@@ -349,6 +357,8 @@ class DeviceAggregatorMixin:
                 kw["upload_vote"] = self.device_upload_vote
             if self.device_upload_fp4 is not None:
                 kw["upload_fp4"] = self.device_upload_fp4
+            if self.device_upload_sketch is not None:
+                kw["upload_sketch"] = self.device_upload_sketch
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = ShardedModelAdapter(model, optimizer=opt, devices=devs, **kw)
@@ -370,6 +380,8 @@ class DeviceAggregatorMixin:
                 kw["upload_vote"] = self.device_upload_vote
             if self.device_upload_fp4 is not None:
                 kw["upload_fp4"] = self.device_upload_fp4
+            if self.device_upload_sketch is not None:
+                kw["upload_sketch"] = self.device_upload_sketch
             if self.device_upload_secagg is not None:
                 kw["upload_secagg"] = self._secagg_spec()
             self.model_wrapper = TorchModelAdapter(model, optimizer=opt, device=dev, **kw)
@@ -608,6 +620,11 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
                          self.device_upload_fp4)
+        if self.device_upload_sketch is not None:
+            from ...sketch_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round: a stale client's base is not this round's model)",
+                         self.device_upload_sketch)
         if self.device_upload_secagg is not None:
             from ...secagg_round import refuse
 

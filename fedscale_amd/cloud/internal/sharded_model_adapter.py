@@ -85,7 +85,7 @@ class ShardedModelAdapter(TorchModelAdapter):
                  upload_quant: Optional[str] = None, upload_topk: Optional[float] = None, upload_secagg=None,
                  upload_sign: Optional[str] = None, upload_rotate: Optional[str] = None,
                  upload_lowrank: Optional[int] = None, upload_vote=None,
-                 upload_fp4: Optional[str] = None):
+                 upload_fp4: Optional[str] = None, upload_sketch=None):
         if upload_dtype is not None:  # 16-bit uploads (fedscale_amd/half_round.py): one whole model on one device
             from ...half_round import refuse
 
@@ -122,6 +122,10 @@ class ShardedModelAdapter(TorchModelAdapter):
             from ...quant4_round import check_format4, refuse
 
             raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", check_format4(upload_fp4))
+        if upload_sketch is not None:  # Count-Sketch uploads (fedscale_amd/sketch_round.py): likewise
+            from ...sketch_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)", upload_sketch)
         if devices is None:
             devices = list(range(torch.cuda.device_count()))
         self.group = devices if isinstance(devices, DeviceGroup) else DeviceGroup(devices, transport)

@@ -279,6 +279,32 @@ def _rebuild_with_upload_fp4(cls, model, optimizer, fmt):
     return cls(model, optimizer, upload_fp4=fmt)
 
 
+def _takes_upload_sketch(init):
+    """``TorchModelAdapter.__init__`` with one more option, the keyword-only ``upload_sketch`` — wired as
+    ``_takes_upload_fp4`` wires its option: set on the instance before the constructor's body runs (which refuses
+    what it does not combine with); an adapter that has it pickles through ``_rebuild_with_upload_sketch``."""
+
+    @functools.wraps(init)
+    def __init__(self, *args, upload_sketch=None, **kw):
+        if upload_sketch is not None:
+            from ...sketch_round import SketchSpec
+
+            self.upload_sketch = SketchSpec.of(upload_sketch)
+        init(self, *args, **kw)
+
+    return __init__
+
+
+def _rebuild_with_upload_sketch(cls, model, optimizer, spec, state):
+    """Unpickle an adapter with ``upload_sketch`` (``TorchModelAdapter.__reduce__``); ``state``: None, or the server's
+    (S_u, S_e) tables as host arrays."""
+    adapter = cls(model, optimizer, upload_sketch=spec)
+    if state is not None:
+        with adapter.dstream.joined():
+            adapter._sketch_tables().load(*state)
+    return adapter
+
+
 class TorchModelAdapter(ModelAdapterBase):
     """``dstream``: the ``DeviceStream`` (GPU + HIP stream) every kernel, copy and event of this adapter is
     issued on — made for ``device`` when not given; a ``ShardedModelAdapter`` hands each part its own.  Each
@@ -311,9 +337,14 @@ class TorchModelAdapter(ModelAdapterBase):
     #: "mxfp4": the clients upload MXFP4-quantised deltas against the round's model, 17/32 byte per parameter (None:
     #: whole weights)
     upload_fp4 = None
+    #: a ``SketchSpec``: the clients upload a Count Sketch of their update against the round's model and keep no state;
+    #: the round is FetchSGD's server step, whose momentum and error-feedback tables this adapter owns (None: whole
+    #: weights)
+    upload_sketch = None
     #: counter of the noise stream the next norm-clipped round draws from (``begin_round(clip=...)``)
     clip_noise_offset = 0
 
+    @_takes_upload_sketch
     @_takes_upload_fp4
     @_takes_upload_vote
     @_takes_upload_lowrank
@@ -358,7 +389,12 @@ class TorchModelAdapter(ModelAdapterBase):
         ``upload_fp4`` (keyword only, taken by ``_takes_upload_fp4``; "mxfp4"; None: whole weights): clients upload
         their update against the weights they were sent for this round, quantised to MXFP4
         (fedscale_amd/cloud/execution/quant4_upload.py); ``begin_round`` then returns a ``Quant4Round`` over a
-        ``Quant4Staging`` (fedscale_amd/quant4_round.py)."""
+        ``Quant4Staging`` (fedscale_amd/quant4_round.py).
+        ``upload_sketch`` (keyword only, taken by ``_takes_upload_sketch``; a ``SketchSpec`` or True for its defaults;
+        None: whole weights): clients upload a Count Sketch of their update against the weights they were sent for
+        this round and keep no state (fedscale_amd/cloud/execution/sketch_upload.py); ``begin_round`` then returns a
+        ``SketchRound`` over a ``SketchStaging`` (fedscale_amd/sketch_round.py), whose finish is FetchSGD's server
+        step over the momentum and error-feedback tables this adapter keeps between rounds."""
         self.model = model
         self.optimizer = optimizer
         self.upload_dtype = None
@@ -489,6 +525,32 @@ class TorchModelAdapter(ModelAdapterBase):
                 raise refuse_4("a sharded model or client-sharded ranks (ShardGroup)", fp4)
             if optimizer is not None and getattr(optimizer, "mode", None) == "q-fedavg":
                 raise refuse_4("the q-fedavg server optimizer", fp4)
+        sketch = self.__dict__.get("upload_sketch")  # set by _takes_upload_sketch before this body runs
+        if sketch is not None:
+            from ...sketch_round import refuse as refuse_k
+
+            if self.upload_dtype is not None:
+                raise refuse_k(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)", sketch)
+            if self.upload_quant is not None:
+                raise refuse_k(f"upload_quant={self.upload_quant!r} (MXFP8 delta uploads)", sketch)
+            if topk is not None:
+                raise refuse_k(f"upload_topk={topk!r} (top-k sparse delta uploads)", sketch)
+            if self.__dict__.get("upload_secagg") is not None:
+                raise refuse_k("upload_secagg (secure-aggregation uploads)", sketch)
+            if sign is not None:
+                raise refuse_k(f"upload_sign={sign!r} (1-bit sign delta uploads)", sketch)
+            if lowrank is not None:
+                raise refuse_k(f"upload_lowrank={lowrank!r} (low-rank delta uploads)", sketch)
+            if vote is not None:
+                raise refuse_k(f"upload_vote={vote!r} (majority-vote sign uploads)", sketch)
+            if fp4 is not None:
+                raise refuse_k(f"upload_fp4={fp4!r} (MXFP4 delta uploads)", sketch)
+            if shards is not None and shards.world != 1:
+                raise refuse_k("a sharded model or client-sharded ranks (ShardGroup)", sketch)
+            mode = getattr(optimizer, "mode", None) if optimizer is not None else None
+            if mode in _STEP_MODES:  # (any other mode is FedAvg on the server, as in set_weights and _apply_round)
+                raise refuse_k(f"the {mode} server optimizer (gradient_policy)", sketch)
+            self._sketch_state = None  # the server's SketchState, made by the first round (_sketch_tables)
         #: counter of the noise stream the next norm-clipped round draws from (clip_round.ClippedRound); every applied
         #: clipped round advances it by round_up(P, 2), so no round reuses an earlier round's draws
         self.clip_noise_offset = 0
@@ -616,6 +678,8 @@ class TorchModelAdapter(ModelAdapterBase):
             nf, ns = self._scratch_buffers()
             nf.copy_(cur_f)
             ns.copy_(cur_s.to(torch.float32).to(torch.int64))  # float32 -> int64 load truncates (:31-35)
+            if self.__dict__.get("_sketch_state") is not None:
+                self._sketch_state.zero()  # momentum and error feedback of a model that is gone
             self._commit_scratch()
 
     def _copy_to_host(self, f_cpu: torch.Tensor, s_cpu: torch.Tensor):
@@ -804,6 +868,13 @@ class TorchModelAdapter(ModelAdapterBase):
         """Pickle like the reference adapter (model + optimizer): the aggregator sizes simulated model
         transfers with ``sys.getsizeof(pickle.dumps(self.model_wrapper))`` (aggregator.py:422-424), so the
         device buffers must not inflate it.  Unpickling rebuilds the HBM state on the current device."""
+        if getattr(self, "upload_sketch", None) is not None:
+            state = self.__dict__.get("_sketch_state")
+            if state is not None:  # the server's tables travel with the adapter, as a server optimizer's state does
+                with self.dstream.joined():
+                    state = state.host()
+            return (_rebuild_with_upload_sketch, (self.__class__, self.get_model(), self.optimizer,
+                                                  self.upload_sketch, state))
         if getattr(self, "upload_fp4", None) is not None:
             return (_rebuild_with_upload_fp4, (self.__class__, self.get_model(), self.optimizer, self.upload_fp4))
         if getattr(self, "upload_vote", None) is not None:
@@ -854,6 +925,8 @@ class TorchModelAdapter(ModelAdapterBase):
             return self._begin_vote_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
         if getattr(self, "upload_fp4", None) is not None:
             return self._begin_fp4_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
+        if getattr(self, "upload_sketch", None) is not None:
+            return self._begin_sketch_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
         if geomed is not None:
             geomed = self._check_geomed(policy, signatures, clip, trim, krum, geomed)
             geomed.resolve(K)  # (a K the round cannot take is refused here, with nothing allocated)
@@ -1261,6 +1334,56 @@ class TorchModelAdapter(ModelAdapterBase):
         return Quant4Round(self.layout, self.device, K, policy, staging=self.staging,
                            last_f32=self._snapshot().f32, capacity=want, dstream=self.dstream)
 
+    def _sketch_tables(self):
+        """The server's ``SketchState`` of an adapter with ``upload_sketch`` (made zero on first use, on the adapter's
+        stream)."""
+        from ...sketch_round import SketchState
+
+        if self._sketch_state is None:
+            spec = self.upload_sketch
+            self._sketch_state = SketchState(spec.rows, spec.cols_for(self.layout.P), self.device)
+        return self._sketch_state
+
+    def _begin_sketch_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
+                            geomed):
+        """``begin_round`` of an adapter with ``upload_sketch``: a ``SketchRound`` over a ``SketchStaging`` whose
+        default capacity is computed from rows of ``rows * cols`` floats.  The combinations the Count-Sketch path does
+        not take are refused here, before a device is touched."""
+        from ...sketch_round import SketchRound, SketchStaging, default_capacity_sketch, refuse
+
+        spec = self.upload_sketch
+        if clip is not None:
+            raise refuse("clip (a norm-clipped round)", spec)
+        if trim is not None:
+            raise refuse("trim (a trimmed-mean round)", spec)
+        if krum is not None:
+            raise refuse("krum (a Multi-Krum round)", spec)
+        if geomed is not None:
+            raise refuse("geomed (a geometric-median round)", spec)
+        if signatures:
+            raise refuse("cohort signatures", spec)
+        if policy != "fedavg":  # fedbuff: a stale client's base is not the model this round starts from
+            raise refuse(f"a {policy} round", spec)
+        if self.shards.world != 1 or self.layout.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)", spec)
+        mode = getattr(self.optimizer, "mode", None) if self.optimizer is not None else None
+        if mode in _STEP_MODES:
+            raise refuse(f"the {mode} server optimizer (gradient_policy)", spec)
+        cap = capacity or self.staging_capacity
+        if cap:
+            want = min(cap, K)
+        elif self.staging is not None and self.staging.capacity >= K:
+            want = K
+        else:
+            want = default_capacity_sketch(self.layout, K, spec.rows * spec.cols_for(self.layout.P), self.device)
+        with self.dstream.joined():
+            state = self._sketch_tables()
+        if self.staging is None or self.staging.capacity < want:
+            self.staging = None
+            self.staging = SketchStaging(self.layout, self.device, want, spec, dstream=self.dstream)
+        return SketchRound(self.layout, self.device, K, policy, spec, staging=self.staging,
+                           last_f32=self._snapshot().f32, state=state, capacity=want, dstream=self.dstream)
+
     def _begin_secagg_round(self, K: int, policy: str, capacity: Optional[int], signatures: bool, clip, trim, krum,
                             geomed):
         """``begin_round`` of an adapter with ``upload_secagg``: a ``SecAggRound`` over a ``MaskedStaging`` whose
@@ -1375,7 +1498,8 @@ class TorchModelAdapter(ModelAdapterBase):
         elif mode == "q-fedavg":
             raise RuntimeError("q-fedavg optimizer but the round was not staged as q-FedAvg")
         else:
-            host = self._mirror_target()
+            # (a SketchRound's finish is several kernels and may refuse the round: no mirror, egress copies as usual)
+            host = None if getattr(rnd, "upload_sketch", None) is not None else self._mirror_target()
             if not self._finish_small(rnd, denom32, out_f, host):
                 rnd.finalize_mean(denom32, denom64, out=out_f, cur_side=self._mean_s, model_side=out_s,
                                   mirror=None if host is None else host.f)
@@ -1410,6 +1534,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "upload_vote", None) is not None:  # a VoteRound finishes through fvt_finish
             return False
         if getattr(rnd, "upload_fp4", None) is not None:  # a Quant4Round finishes through fcl_finish
+            return False
+        if getattr(rnd, "upload_sketch", None) is not None:  # a SketchRound finishes through FetchSGD's server step
             return False
         if getattr(rnd, "upload_secagg", None) is not None:  # a SecAggRound finishes through fsa_finish
             return False
