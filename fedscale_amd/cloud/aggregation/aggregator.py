@@ -157,6 +157,12 @@ class DeviceAggregatorMixin:
     #: FedAvg and fed-yogi; q-FedAvg, device_clip_norm, device_shards, device_upload_dtype, the async and the cohort
     #: mixin are refused with it
     device_trim = None
+    #: opt-in: device_trim at any depth — 1 <= t, 2t < K <= 4096: 10-20 % per side at K = 1000, the median at any K —
+    #: by one LDS-resident selection pass over the staged rows (fedscale_amd/deep_trim_round.py; INTEGRATION.md, "Deep
+    #: trimmed-mean and median aggregation").  The forms of device_trim; the same bits where both run.  FedAvg, fed-yogi,
+    #: fed-adam, fed-adagrad and fed-avgm; q-FedAvg, device_trim, device_clip_norm, device_krum, device_geomed,
+    #: device_shards, every upload format, the async and the cohort mixin are refused with it
+    device_deep_trim = None
     #: opt-in: Krum / Multi-Krum — every upload is scored by its squared distance to its K - f - 2 nearest other
     #: uploads on the device and only the m best-scored uploads are averaged (fedscale_amd/krum_round.py;
     #: INTEGRATION.md, "Multi-Krum aggregation").  An f (int, or a fraction in [0, 0.5)): Multi-Krum, m = K - f; an
@@ -241,6 +247,32 @@ class DeviceAggregatorMixin:
             raise refuse("device_clip_norm (a norm-clipped round)")
         if self.device_upload_dtype is not None:
             raise refuse(f"device_upload_dtype={self.device_upload_dtype!r} (16-bit uploads)")
+        if self.device_shards is not None and len(self.device_shards) > 1:
+            raise refuse("device_shards (a model sharded over several GPUs)")
+        return spec
+
+    def _deep_trim_spec(self):
+        """The ``DeepTrimSpec`` of this aggregator's rounds (None: ``device_deep_trim`` is not set), after refusing the
+        attributes it does not combine with."""
+        if self.device_deep_trim is None:
+            return None
+        from ...deep_trim_round import DeepTrimSpec, refuse
+
+        spec = DeepTrimSpec(self.device_deep_trim)
+        for attr, what in (("device_trim", "a trimmed-mean round: pick one of the two"),
+                           ("device_clip_norm", "a norm-clipped round"), ("device_krum", "a Multi-Krum round"),
+                           ("device_geomed", "a geometric-median round"),
+                           ("device_upload_secagg", "secure-aggregation uploads"),
+                           ("device_upload_dtype", "16-bit uploads"), ("device_upload_quant", "MXFP8 delta uploads"),
+                           ("device_upload_topk", "top-k sparse delta uploads"),
+                           ("device_upload_sign", "1-bit sign delta uploads"),
+                           ("device_upload_rotate", "rotated 1-bit sign delta uploads"),
+                           ("device_upload_lowrank", "low-rank delta uploads"),
+                           ("device_upload_vote", "majority-vote uploads"),
+                           ("device_upload_fp4", "MXFP4 delta uploads"),
+                           ("device_upload_sketch", "Count-Sketch uploads")):
+            if getattr(self, attr, None) is not None:
+                raise refuse(f"{attr}={getattr(self, attr)!r} ({what})")
         if self.device_shards is not None and len(self.device_shards) > 1:
             raise refuse("device_shards (a model sharded over several GPUs)")
         return spec
@@ -532,6 +564,9 @@ class DeviceAggregatorMixin:
             trim = self._trim_spec()
             if trim is not None:
                 kw["trim"] = trim
+            deep = self._deep_trim_spec()
+            if deep is not None:
+                kw["deep_trim"] = deep
             krum = self._krum_spec()
             if krum is not None:
                 kw["krum"] = krum
@@ -575,6 +610,10 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_trim is not None:
             from ...trim_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
+        if self.device_deep_trim is not None:
+            from ...deep_trim_round import refuse
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_krum is not None:
@@ -673,6 +712,10 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         if self.device_trim is not None:
             from ...trim_round import refuse
+
+            raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
+        if self.device_deep_trim is not None:
+            from ...deep_trim_round import refuse
 
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         if self.device_krum is not None:

@@ -274,7 +274,12 @@ class ShardedModelAdapter(TorchModelAdapter):
 
     # ---- rounds -----------------------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
-                    signatures: bool = False, clip=None, trim=None, krum=None, geomed=None) -> ShardedRound:
+                    signatures: bool = False, clip=None, trim=None, krum=None, geomed=None,
+                    deep_trim=None) -> ShardedRound:
+        if deep_trim is not None:  # deep trimmed rounds (fedscale_amd/deep_trim_round.py): one whole model, one device
+            from ...deep_trim_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)")
         if geomed is not None:  # geometric-median rounds (fedscale_amd/geomed_round.py): one whole model on one device
             from ...geomed_round import refuse
 

@@ -901,7 +901,8 @@ class TorchModelAdapter(ModelAdapterBase):
 
     # ---- device fast path -----------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
-                    signatures: bool = False, clip=None, trim=None, krum=None, geomed=None) -> DeviceRound:
+                    signatures: bool = False, clip=None, trim=None, krum=None, geomed=None,
+                    deep_trim=None) -> DeviceRound:
         """``keep_mean`` for q-FedAvg rounds: True fuses the FedAvg chain when the round spans several chunks
         (the staged updates are then gone by the end of the round), "always" in every round (the mean is then
         independent of the staging's later reuse), False never (model_weights of such rounds raises).
@@ -918,7 +919,13 @@ class TorchModelAdapter(ModelAdapterBase):
         ``KrumRound`` (fedscale_amd/krum_round.py), which needs all K uploads resident.
         ``geomed`` (a ``geomed_round.GeoMedSpec``, an int — its iterations — or True; FedAvg rounds): the new model is
         the geometric median of the uploads by the smoothed Weiszfeld iteration — a ``GeoMedRound``
-        (fedscale_amd/geomed_round.py), which needs all K uploads resident."""
+        (fedscale_amd/geomed_round.py), which needs all K uploads resident.
+        ``deep_trim`` (a ``deep_trim_round.DeepTrimSpec``, or what it takes: a count, a fraction or "median"; FedAvg
+        rounds): ``trim`` at any depth — 1 <= t, 2t < K <= 4096 — by one LDS-resident selection pass over the rows — a
+        ``DeepTrimmedRound`` (fedscale_amd/deep_trim_round.py), which needs all K uploads resident."""
+        if deep_trim is not None:  # (before the upload formats' own rounds: it combines with none of them)
+            deep_trim = self._check_deep_trim(policy, signatures, clip, trim, krum, geomed, deep_trim)
+            deep_trim.count(K)  # (a count the round cannot take is refused here, with nothing allocated)
         if getattr(self, "upload_secagg", None) is not None:
             return self._begin_secagg_round(K, policy, capacity, signatures, clip, trim, krum, geomed)
         if getattr(self, "upload_vote", None) is not None:
@@ -971,6 +978,9 @@ class TorchModelAdapter(ModelAdapterBase):
         if trim is not None and want < K:  # before the staging is (re)allocated, and before any launch
             raise ValueError(f"a trimmed round needs all K={K} uploads resident, the staging capacity is {want}: "
                              f"there is no chunk folding (raise capacity=, or lower K)")
+        if deep_trim is not None and want < K:  # before the staging is (re)allocated, and before any launch
+            raise ValueError(f"a deep trimmed round needs all K={K} uploads resident, the staging capacity is "
+                             f"{want}: there is no chunk folding (raise capacity=, or lower K)")
         if krum is not None and want < K:  # before the staging is (re)allocated, and before any launch
             raise ValueError(f"a Krum round needs all K={K} uploads resident, the staging capacity is {want}: "
                              f"there is no chunk folding (raise capacity=, or lower K)")
@@ -985,6 +995,11 @@ class TorchModelAdapter(ModelAdapterBase):
 
             return TrimmedRound(self.layout, self.device, K, trim, staging=self.staging, capacity=want,
                                 dstream=self.dstream)
+        if deep_trim is not None:
+            from ...deep_trim_round import DeepTrimmedRound
+
+            return DeepTrimmedRound(self.layout, self.device, K, deep_trim, staging=self.staging, capacity=want,
+                                    dstream=self.dstream)
         snap = self._snapshot()
         if krum is not None:
             from ...krum_round import KrumRound
@@ -1036,6 +1051,36 @@ class TorchModelAdapter(ModelAdapterBase):
             raise refuse("clip (a norm-clipped round)")
         if self.upload_dtype is not None:
             raise refuse(f"upload_dtype={self.upload_dtype!r} (16-bit uploads)")
+        if signatures:
+            raise refuse("cohort signatures")
+        if self.shards.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)")
+        if self.layout.world != 1:
+            raise refuse("a parameter-sharded layout")
+        if policy != "fedavg":
+            raise refuse(f"a {policy} round")
+        if self.optimizer is not None and getattr(self.optimizer, "mode", None) == "q-fedavg":
+            raise refuse("the q-fedavg server optimizer")
+        return spec
+
+    def _check_deep_trim(self, policy: str, signatures: bool, clip, trim, krum, geomed, deep_trim):
+        """Refuse, before a device is touched, what a deep trimmed round (``begin_round(deep_trim=...)``) does not
+        take; the ``DeepTrimSpec`` of ``deep_trim``."""
+        from ...deep_trim_round import DeepTrimSpec, refuse
+
+        spec = DeepTrimSpec(deep_trim)
+        for name, given in (("trim (a trimmed-mean round: pick one of the two)", trim),
+                            ("clip (a norm-clipped round)", clip), ("krum (a Multi-Krum round)", krum),
+                            ("geomed (a geometric-median round)", geomed)):
+            if given is not None:
+                raise refuse(name)
+        for attr, what in (("upload_secagg", "secure-aggregation uploads"), ("upload_vote", "majority-vote uploads"),
+                           ("upload_fp4", "MXFP4 delta uploads"), ("upload_sketch", "Count-Sketch uploads"),
+                           ("upload_lowrank", "low-rank delta uploads"), ("upload_sign", "1-bit sign delta uploads"),
+                           ("upload_topk", "top-k sparse delta uploads"), ("upload_quant", "MXFP8 delta uploads"),
+                           ("upload_dtype", "16-bit uploads")):
+            if getattr(self, attr, None) is not None:
+                raise refuse(f"{attr}={getattr(self, attr)!r} ({what})")
         if signatures:
             raise refuse("cohort signatures")
         if self.shards.world != 1:
@@ -1542,6 +1587,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "clip", None) is not None:  # a ClippedRound finishes through fcl_finish
             return False
         if getattr(rnd, "trim", None) is not None:  # a TrimmedRound finishes through ft_reduce
+            return False
+        if getattr(rnd, "deep_trim", None) is not None:  # a DeepTrimmedRound finishes through fdt_reduce
             return False
         if getattr(rnd, "krum", None) is not None:  # a KrumRound finishes through fk_finish
             return False
