@@ -1,0 +1,41 @@
+"""ctypes binding of include/fedbulyan.h — the Bulyan entry points of libfedagg.so.
+
+They are typed onto the library ``_native.load()`` has already loaded and verified (build id, ABI version of
+include/fedagg.h); ``_native.SIGNATURES`` stays the table of fedagg.h / fedclient.h alone.  As there: no fallback,
+a missing symbol or a failing call raises ``FedAggError``.
+"""
+from __future__ import annotations
+
+import ctypes
+
+from . import _native
+
+ABI_VERSION = 1  # include/fedbulyan.h FBL_ABI_VERSION
+PLAN_FIELDS = 7  # FBL_PLAN_FIELDS
+
+_c_void_p, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+
+# name -> (restype, argtypes);  must list every symbol of include/fedbulyan.h
+SIGNATURES = {
+    "fbl_abi_version": (_i32, []),
+    "fbl_select_workspace_bytes": (_i64, [_i32]),
+    "fbl_select": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p]),
+    "fbl_reduce": (_i32, [_c_void_p, _i64, _i32, _i64, _c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p,
+                          _c_void_p, _c_void_p, _i32, _c_void_p]),
+    "fbl_plan": (_i32, [_i32, _i32, _i64, _c_void_p]),
+}
+
+_lib = None
+
+
+def load():
+    """The loaded library with the fbl_* entry points typed (once; a racing second typing sets the same types)."""
+    global _lib
+    if _lib is None:
+        _lib = _native.bind_header(SIGNATURES, "fbl_abi_version", ABI_VERSION, "fedbulyan")
+    return _lib
+
+
+def call(name: str, *args):
+    """Call an fbl_* entry point; raise on a negative return code (byte counts are returned)."""
+    return _native.checked_call(load(), name, args, negative_only=True)

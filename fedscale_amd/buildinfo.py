@@ -28,14 +28,15 @@ SRCS = ("fedscale_amd/csrc/fedagg.hip", "fedscale_amd/csrc/client_update.hip", "
         "fedscale_amd/csrc/geomed.hip", "fedscale_amd/csrc/secagg.hip", "fedscale_amd/csrc/sign_reduce.hip",
         "fedscale_amd/csrc/rotate.hip", "fedscale_amd/csrc/server_opt.hip", "fedscale_amd/csrc/lowrank_reduce.hip",
         "fedscale_amd/csrc/vote_reduce.hip", "fedscale_amd/csrc/quant4_reduce.hip", "fedscale_amd/csrc/sketch.hip",
-        "fedscale_amd/csrc/deep_trim.hip")
+        "fedscale_amd/csrc/deep_trim.hip", "fedscale_amd/csrc/bulyan.hip")
 #: headers they include (every #include "..." of the library)
 HDRS = ("fedscale_amd/csrc/fa_device.h", "fedscale_amd/csrc/fa_common.h", "include/fedagg.h", "include/fedclient.h",
         "include/fedcohort.h", "include/fedhalf.h", "include/fedclip.h", "include/fedtrim.h", "include/fedquant.h",
         "include/fedsparse.h", "include/fedkrum.h", "include/fedgeomed.h",
         "include/fedsecagg.h", "include/fedsign.h", "include/fedrotate.h",
         "include/fedserveropt.h", "include/fedlowrank.h", "include/fedvote.h",
-        "include/fedquant4.h", "include/fedsketch.h", "include/feddeeptrim.h")
+        "include/fedquant4.h", "include/fedsketch.h", "include/feddeeptrim.h",
+        "include/fedbulyan.h")
 FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall")
 LIB = os.path.join(ROOT, "fedscale_amd", "libfedagg.so")
 MARKER = b"FA_BUILD_ID="

@@ -163,6 +163,12 @@ class DeviceAggregatorMixin:
     #: fed-adam, fed-adagrad and fed-avgm; q-FedAvg, device_trim, device_clip_norm, device_krum, device_geomed,
     #: device_shards, every upload format, the async and the cohort mixin are refused with it
     device_deep_trim = None
+    #: opt-in: Bulyan — Krum run K - 2f - 2 times on the device, the winner removed each time, then for every parameter
+    #: the mean of the K - 4f - 2 selected values closest to their median (fedscale_amd/bulyan_round.py; INTEGRATION.md,
+    #: "Bulyan aggregation").  An int f, the uploads assumed bad, 4f + 3 <= K; or a BulyanSpec.  FedAvg, fed-yogi,
+    #: fed-adam, fed-adagrad and fed-avgm; q-FedAvg, every other device_* aggregation rule, device_shards, every upload
+    #: format, the async and the cohort mixin are refused with it
+    device_bulyan = None
     #: opt-in: Krum / Multi-Krum — every upload is scored by its squared distance to its K - f - 2 nearest other
     #: uploads on the device and only the m best-scored uploads are averaged (fedscale_amd/krum_round.py;
     #: INTEGRATION.md, "Multi-Krum aggregation").  An f (int, or a fraction in [0, 0.5)): Multi-Krum, m = K - f; an
@@ -260,6 +266,32 @@ class DeviceAggregatorMixin:
 
         spec = DeepTrimSpec(self.device_deep_trim)
         for attr, what in (("device_trim", "a trimmed-mean round: pick one of the two"),
+                           ("device_clip_norm", "a norm-clipped round"), ("device_krum", "a Multi-Krum round"),
+                           ("device_geomed", "a geometric-median round"),
+                           ("device_upload_secagg", "secure-aggregation uploads"),
+                           ("device_upload_dtype", "16-bit uploads"), ("device_upload_quant", "MXFP8 delta uploads"),
+                           ("device_upload_topk", "top-k sparse delta uploads"),
+                           ("device_upload_sign", "1-bit sign delta uploads"),
+                           ("device_upload_rotate", "rotated 1-bit sign delta uploads"),
+                           ("device_upload_lowrank", "low-rank delta uploads"),
+                           ("device_upload_vote", "majority-vote uploads"),
+                           ("device_upload_fp4", "MXFP4 delta uploads"),
+                           ("device_upload_sketch", "Count-Sketch uploads")):
+            if getattr(self, attr, None) is not None:
+                raise refuse(f"{attr}={getattr(self, attr)!r} ({what})")
+        if self.device_shards is not None and len(self.device_shards) > 1:
+            raise refuse("device_shards (a model sharded over several GPUs)")
+        return spec
+
+    def _bulyan_spec(self):
+        """The ``BulyanSpec`` of this aggregator's rounds (None: ``device_bulyan`` is not set), after refusing the
+        attributes it does not combine with."""
+        if self.device_bulyan is None:
+            return None
+        from ...bulyan_round import BulyanSpec, refuse
+
+        spec = BulyanSpec(self.device_bulyan)
+        for attr, what in (("device_trim", "a trimmed-mean round"), ("device_deep_trim", "a deep trimmed-mean round"),
                            ("device_clip_norm", "a norm-clipped round"), ("device_krum", "a Multi-Krum round"),
                            ("device_geomed", "a geometric-median round"),
                            ("device_upload_secagg", "secure-aggregation uploads"),
@@ -559,8 +591,11 @@ class DeviceAggregatorMixin:
                     raise ValueError(f"device_upload_secagg={secagg!r} but the model wrapper was built with "
                                      f"upload_secagg={getattr(w, 'upload_secagg', None)!r}")
             self._secagg_clients = []  # a masked round's client ids, in arrival order (device_secagg_unmask)
+            bulyan = self._bulyan_spec()  # (refuses every other device_* option, before any of them is looked at)
             clip = self._clip_spec()
             kw = {} if clip is None else {"clip": clip}  # (unset, the call is what it was)
+            if bulyan is not None:
+                kw["bulyan"] = bulyan
             trim = self._trim_spec()
             if trim is not None:
                 kw["trim"] = trim
@@ -614,6 +649,10 @@ class DeviceAsyncAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_deep_trim is not None:
             from ...deep_trim_round import refuse
+
+            raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
+        if self.device_bulyan is not None:
+            from ...bulyan_round import refuse
 
             raise refuse("DeviceAsyncAggregatorMixin (a fedbuff round)")
         if self.device_krum is not None:
@@ -716,6 +755,10 @@ class DeviceCohortAggregatorMixin(DeviceAggregatorMixin):
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         if self.device_deep_trim is not None:
             from ...deep_trim_round import refuse
+
+            raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
+        if self.device_bulyan is not None:
+            from ...bulyan_round import refuse
 
             raise refuse("DeviceCohortAggregatorMixin (per-cohort rounds)")
         if self.device_krum is not None:

@@ -275,7 +275,11 @@ class ShardedModelAdapter(TorchModelAdapter):
     # ---- rounds -----------------------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
                     signatures: bool = False, clip=None, trim=None, krum=None, geomed=None,
-                    deep_trim=None) -> ShardedRound:
+                    deep_trim=None, bulyan=None) -> ShardedRound:
+        if bulyan is not None:  # Bulyan rounds (fedscale_amd/bulyan_round.py): one whole model on one device
+            from ...bulyan_round import refuse
+
+            raise refuse("ShardedModelAdapter (a model sharded over several GPUs)")
         if deep_trim is not None:  # deep trimmed rounds (fedscale_amd/deep_trim_round.py): one whole model, one device
             from ...deep_trim_round import refuse
 

@@ -902,7 +902,7 @@ class TorchModelAdapter(ModelAdapterBase):
     # ---- device fast path -----------------------------------------------------------------------
     def begin_round(self, K: int, policy: str, capacity: Optional[int] = None, keep_mean=True,
                     signatures: bool = False, clip=None, trim=None, krum=None, geomed=None,
-                    deep_trim=None) -> DeviceRound:
+                    deep_trim=None, bulyan=None) -> DeviceRound:
         """``keep_mean`` for q-FedAvg rounds: True fuses the FedAvg chain when the round spans several chunks
         (the staged updates are then gone by the end of the round), "always" in every round (the mean is then
         independent of the staging's later reuse), False never (model_weights of such rounds raises).
@@ -922,7 +922,14 @@ class TorchModelAdapter(ModelAdapterBase):
         (fedscale_amd/geomed_round.py), which needs all K uploads resident.
         ``deep_trim`` (a ``deep_trim_round.DeepTrimSpec``, or what it takes: a count, a fraction or "median"; FedAvg
         rounds): ``trim`` at any depth — 1 <= t, 2t < K <= 4096 — by one LDS-resident selection pass over the rows — a
-        ``DeepTrimmedRound`` (fedscale_amd/deep_trim_round.py), which needs all K uploads resident."""
+        ``DeepTrimmedRound`` (fedscale_amd/deep_trim_round.py), which needs all K uploads resident.
+        ``bulyan`` (a ``bulyan_round.BulyanSpec``, or an int — the uploads f assumed bad; FedAvg rounds): Krum run
+        K - 2f - 2 times, the winner removed each time, then per parameter the mean of the K - 4f - 2 selected values
+        closest to their median — a ``BulyanRound`` (fedscale_amd/bulyan_round.py), which needs all K uploads
+        resident."""
+        if bulyan is not None:  # (before the upload formats' own rounds: it combines with none of them)
+            bulyan = self._check_bulyan(policy, signatures, clip, trim, krum, geomed, deep_trim, bulyan)
+            bulyan.counts(K)  # (an f the round cannot take is refused here, with nothing allocated)
         if deep_trim is not None:  # (before the upload formats' own rounds: it combines with none of them)
             deep_trim = self._check_deep_trim(policy, signatures, clip, trim, krum, geomed, deep_trim)
             deep_trim.count(K)  # (a count the round cannot take is refused here, with nothing allocated)
@@ -981,6 +988,9 @@ class TorchModelAdapter(ModelAdapterBase):
         if deep_trim is not None and want < K:  # before the staging is (re)allocated, and before any launch
             raise ValueError(f"a deep trimmed round needs all K={K} uploads resident, the staging capacity is "
                              f"{want}: there is no chunk folding (raise capacity=, or lower K)")
+        if bulyan is not None and want < K:  # before the staging is (re)allocated, and before any launch
+            raise ValueError(f"a Bulyan round needs all K={K} uploads resident, the staging capacity is {want}: "
+                             f"there is no chunk folding (raise capacity=, or lower K)")
         if krum is not None and want < K:  # before the staging is (re)allocated, and before any launch
             raise ValueError(f"a Krum round needs all K={K} uploads resident, the staging capacity is {want}: "
                              f"there is no chunk folding (raise capacity=, or lower K)")
@@ -1001,6 +1011,11 @@ class TorchModelAdapter(ModelAdapterBase):
             return DeepTrimmedRound(self.layout, self.device, K, deep_trim, staging=self.staging, capacity=want,
                                     dstream=self.dstream)
         snap = self._snapshot()
+        if bulyan is not None:
+            from ...bulyan_round import BulyanRound
+
+            return BulyanRound(self.layout, self.device, K, bulyan, staging=self.staging, last_f32=snap.f32,
+                               capacity=want, dstream=self.dstream)
         if krum is not None:
             from ...krum_round import KrumRound
 
@@ -1072,6 +1087,36 @@ class TorchModelAdapter(ModelAdapterBase):
         for name, given in (("trim (a trimmed-mean round: pick one of the two)", trim),
                             ("clip (a norm-clipped round)", clip), ("krum (a Multi-Krum round)", krum),
                             ("geomed (a geometric-median round)", geomed)):
+            if given is not None:
+                raise refuse(name)
+        for attr, what in (("upload_secagg", "secure-aggregation uploads"), ("upload_vote", "majority-vote uploads"),
+                           ("upload_fp4", "MXFP4 delta uploads"), ("upload_sketch", "Count-Sketch uploads"),
+                           ("upload_lowrank", "low-rank delta uploads"), ("upload_sign", "1-bit sign delta uploads"),
+                           ("upload_topk", "top-k sparse delta uploads"), ("upload_quant", "MXFP8 delta uploads"),
+                           ("upload_dtype", "16-bit uploads")):
+            if getattr(self, attr, None) is not None:
+                raise refuse(f"{attr}={getattr(self, attr)!r} ({what})")
+        if signatures:
+            raise refuse("cohort signatures")
+        if self.shards.world != 1:
+            raise refuse("a sharded model or client-sharded ranks (ShardGroup)")
+        if self.layout.world != 1:
+            raise refuse("a parameter-sharded layout")
+        if policy != "fedavg":
+            raise refuse(f"a {policy} round")
+        if self.optimizer is not None and getattr(self.optimizer, "mode", None) == "q-fedavg":
+            raise refuse("the q-fedavg server optimizer")
+        return spec
+
+    def _check_bulyan(self, policy: str, signatures: bool, clip, trim, krum, geomed, deep_trim, bulyan):
+        """Refuse, before a device is touched, what a Bulyan round (``begin_round(bulyan=...)``) does not take; the
+        ``BulyanSpec`` of ``bulyan``."""
+        from ...bulyan_round import BulyanSpec, refuse
+
+        spec = BulyanSpec(bulyan)
+        for name, given in (("clip (a norm-clipped round)", clip), ("trim (a trimmed-mean round)", trim),
+                            ("krum (a Multi-Krum round)", krum), ("geomed (a geometric-median round)", geomed),
+                            ("deep_trim (a deep trimmed-mean round)", deep_trim)):
             if given is not None:
                 raise refuse(name)
         for attr, what in (("upload_secagg", "secure-aggregation uploads"), ("upload_vote", "majority-vote uploads"),
@@ -1589,6 +1634,8 @@ class TorchModelAdapter(ModelAdapterBase):
         if getattr(rnd, "trim", None) is not None:  # a TrimmedRound finishes through ft_reduce
             return False
         if getattr(rnd, "deep_trim", None) is not None:  # a DeepTrimmedRound finishes through fdt_reduce
+            return False
+        if getattr(rnd, "bulyan", None) is not None:  # a BulyanRound finishes through fbl_reduce
             return False
         if getattr(rnd, "krum", None) is not None:  # a KrumRound finishes through fk_finish
             return False
